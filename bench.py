@@ -10,6 +10,12 @@ reference filter, 2x2 footprint packing, initial cost, 5 x 4 sweeps, extraction)
 
 Prints ONE JSON line (rank 0). See DESIGN.md "Measurement" for the derivation of
 roofline.achieved (algorithmic bytes per sweep launch) and the CPU baseline sample.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line (PatchMatch
+throughput + the roofline figures of those same steps). Everything else -- the CPU
+baselines, the reference build, the seam, geometric, fusion and bundle-adjustment legs --
+runs only with `--full` (the `--no-*` flags prune it there). `--dump-outputs DIR` writes the
+depth / normal maps of the last timed step (a fixed, seeded pixel sample) as DIR/*.npy.
 """
 from __future__ import annotations
 
@@ -31,6 +37,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs: CPU baselines, seam, geometric + fusion, bundle adjustment "
+                         "(off: only the timed PatchMatch steps and their roofline figures)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the depth / normal maps of the last step (a fixed, seeded "
+                         "pixel sample, <= 48 MB) as DIR/<name>.npy")
     ap.add_argument("--width", type=int, default=2560)
     ap.add_argument("--height", type=int, default=1920)
     ap.add_argument("--num-src", type=int, default=20)
@@ -63,6 +75,15 @@ def parse():
     return ap.parse_args()
 
 
+def cpu_threads():
+    """Host threads of the CPU legs: OMP_NUM_THREADS where the environment sets it, else the CPUs this process may run
+    on (os.cpu_count() counts the whole machine's, and a pool larger than the CPUs it gets only slows itself down)."""
+    n = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
+    if n.isdigit() and int(n) > 0:
+        return int(n)
+    return len(os.sched_getaffinity(0)) or 1
+
+
 def cpu_baseline(views, ref, src, dmin, dmax, crop_wh):
     """Oracle (CPU restatement, all host cores) on a bounded sample of the same workload:
     a centre crop of one full-resolution reference image against its full-resolution
@@ -83,7 +104,7 @@ def cpu_baseline(views, ref, src, dmin, dmax, crop_wh):
         else:
             imgs.append(dict(K=vv.K, R=vv.R, T=vv.T, gray=vv.gray))
     o = pm_oracle.default_options(depth_min=dmin, depth_max=dmax, geom_consistency=0, filter=1)
-    o.num_threads = os.cpu_count() or 0   # every host core (importing torch caps OpenMP's default at the physical cores)
+    o.num_threads = cpu_threads()   # every host thread it may use (importing torch caps OpenMP's default at the physical cores)
     t = time.time()
     pm_oracle.run(o, imgs, ref, src)
     dt = time.time() - t
@@ -244,7 +265,7 @@ def ba_secondary(a, local_rank, with_cpu, rank=0, world=1, dev=None):
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import ba_oracle
             c1 = fp1.copy()
-            o1 = est.solve_flat(c1, est.SolverOptions(max_num_iterations=9), solve_fn=ba_oracle.solve_fn, num_threads=os.cpu_count() or 0)
+            o1 = est.solve_flat(c1, est.SolverOptions(max_num_iterations=9), solve_fn=ba_oracle.solve_fn, num_threads=cpu_threads())
             h1 = est.solve_flat(fp1.copy(), est.SolverOptions(max_num_iterations=9), gpu_index=local_rank)
             m1 = min(len(o1.log_cost), len(h1.log_cost))
             out["shared_intrinsics"]["hip_vs_oracle_max_rel_cost_diff"] = \
@@ -276,7 +297,7 @@ def ba_secondary(a, local_rank, with_cpu, rank=0, world=1, dev=None):
         import ba_oracle
         c = fp.copy()
         sc = est.solve_flat(c, est.SolverOptions(max_num_iterations=9), solve_fn=ba_oracle.solve_fn,
-                            num_threads=os.cpu_count() or 0)  # ~10 s on the box's host cores (all of them)
+                            num_threads=cpu_threads())  # under a second per iteration on 16 host threads
         # parity on the benchmark problem itself: the HIP cost log of the same 9 iterations against the oracle's
         sh = est.solve_flat(fp.copy(), est.SolverOptions(max_num_iterations=9), gpu_index=local_rank)
         m = min(len(sc.log_cost), len(sh.log_cost))
@@ -342,7 +363,7 @@ def ba2_leg(a, local_rank, with_cpu):
         f10 = est.FlatProblem.from_arrays(d10)
         est.fix_gauge_two_cams(f10)
         o10 = est.solve_flat(f10.copy(), est.SolverOptions(max_num_iterations=3), solve_fn=ba_oracle.solve_fn,
-                             num_threads=os.cpu_count() or 0)
+                             num_threads=cpu_threads())
         h10 = est.solve_flat(f10.copy(), est.SolverOptions(max_num_iterations=3), gpu_index=local_rank)
         m = min(len(o10.log_cost), len(h10.log_cost))
         out["parity_at_one_tenth"] = {
@@ -610,9 +631,11 @@ def fusion_leg(a, views, fmaps, with_cpu=True):
         ov = [[j for j in range(n) if j != i] for i in range(n)]
         # the reference's own multi-threaded path (mvs/fusion.cc:247-269: ThreadPool(num_threads), default all cores;
         # oracle mode 3 = real threads racing on the masks as the reference's do) on the SAME images, end to end
-        cores = os.cpu_count() or 1
+        cores = cpu_threads()
+        opt_mt = fusion.StereoFusionOptions()
+        opt_mt.num_threads = cores
         t = time.time()
-        ref_mt = fusion_oracle.fuse(opt, imgs, ov, mode=3)
+        ref_mt = fusion_oracle.fuse(opt_mt, imgs, ov, mode=3)
         dmt = time.time() - t
         m = min(4, n)
         sub = imgs[:m]
@@ -627,6 +650,34 @@ def fusion_leg(a, views, fmaps, with_cpu=True):
                                             "sample": f"mode 0 (row-major, one thread) on the first {m} images, "
                                                       f"{len(ref.xyz)} points"}}
     return out
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # all arrays of --dump-outputs together
+
+
+def dump_outputs(path, pms):
+    """What a caller of the timed path receives for the problems of the last timed step: each reference image's depth
+    map (H, W) and normal map (3, H, W), float32 (GetDepthMap / GetNormalMap). A fixed, seeded sample of the pixels --
+    the same for every problem and every run of the same arguments -- keeps the files within DUMP_BUDGET_BYTES:
+      depth.npy        (problems, P)      depth at the sampled pixels
+      normal.npy       (problems, 3, P)   normal at the sampled pixels
+      pixel_index.npy  (P,)               row-major index y * W + x of the sampled pixels (float64, exact)
+      ref_image.npy    (problems,)        index of each problem's reference image in this rank's window"""
+    H, W, _ = pms[0]._dims
+    n_pix = H * W
+    per_pixel = 4 * 4 * len(pms)   # depth + three normal components, float32, per problem
+    P = min(n_pix, max(1, (DUMP_BUDGET_BYTES - 8 * len(pms)) // (per_pixel + 8)))
+    idx = np.sort(np.random.default_rng(20240).choice(n_pix, size=P, replace=False)) if P < n_pix else np.arange(n_pix)
+    depth = np.empty((len(pms), P), np.float32)
+    normal = np.empty((len(pms), 3, P), np.float32)
+    for i, pm in enumerate(pms):
+        depth[i] = pm.GetDepthMap().reshape(-1)[idx]
+        normal[i] = pm.GetNormalMap().reshape(3, -1)[:, idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "depth.npy"), depth)
+    np.save(os.path.join(path, "normal.npy"), normal)
+    np.save(os.path.join(path, "pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "ref_image.npy"), np.array([pm.problem_.ref_image_idx for pm in pms], np.float64))
 
 
 def spawn_command(gpus, argv, port, script=None):
@@ -646,9 +697,10 @@ def check_world(gpus, world):
 
 
 def spawn_ranks(a):
-    """`python bench.py --gpus N` (N > 1) without a launcher around it: become the launcher. Re-executes
-    this script under torch.distributed.run with one rank per GPU (RCCL over xGMI); rank 0 of that job
-    prints the single JSON line, `n_gpus` in it is the world size RCCL saw."""
+    """`python bench.py --gpus N` (N > 1) without a launcher around it: become the launcher. Runs this
+    script under torch.distributed.run in a child process, one rank per GPU (RCCL over xGMI), and exits
+    with its status; rank 0 of that job prints the single JSON line, `n_gpus` in it is the world size
+    RCCL saw."""
     import socket
     n_dev = torch.cuda.device_count()
     if n_dev < a.gpus:
@@ -658,7 +710,8 @@ def spawn_ranks(a):
         port = sock.getsockname()[1]
     cmd, env = spawn_command(a.gpus, sys.argv[1:], port)
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    import subprocess
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def main():
@@ -721,7 +774,8 @@ def main():
     kernel_names = set()   # sweep kernels the timed steps launched (the library reports what it ran)
     launch_shape = [a.batch, 1]   # reference images per sweep launch, launches in flight together (pm_get_launch_shape)
 
-    def run_step(step, record):
+    def run_step(step, record, keep=False):
+        """keep: leave the problems open and return them (their maps are read after the timer stopped)."""
         nonlocal sweep_ms, sweep_n, evals_sweep, evals_init
         grps = [[problem((step * a.groups + g) * a.batch + b)[0] for b in range(a.batch)]
                 for g in range(a.groups)]
@@ -744,6 +798,8 @@ def main():
                     a_, b_ = pm.GetEvaluationCount()
                     evals_sweep += a_
                     evals_init += b_
+        if keep:
+            return [pm for pms in grps for pm in pms]
         for pms in grps:
             for pm in pms:
                 pm.close()
@@ -752,10 +808,16 @@ def main():
         run_step(w, False)
     barrier()
     t0 = time.time()
+    last = None
     for k in range(a.steps):
-        run_step(a.warmup + k, True)
+        last = run_step(a.warmup + k, True, keep=bool(a.dump_outputs) and k == a.steps - 1)
     barrier()
     dt = time.time() - t0
+    if last is not None:
+        if rank == 0:
+            dump_outputs(a.dump_outputs, last)
+        for pm in last:
+            pm.close()
     dt = D.max_over_ranks(dt, dev)
     images_done = sum(D.gather_counts(a.steps * a.batch * a.groups, dev))
 
@@ -826,28 +888,28 @@ def main():
                         "image layout (DESIGN.md 1.5)",
             },
         }
-        # the CPU baseline and the secondary (single-GPU) BA measurement belong to the N = 1 run only
-        if not a.no_cpu_baseline and world == 1:
+        # the CPU baseline and the secondary (single-GPU) legs belong to the N = 1 run with --full only
+        if a.full and not a.no_cpu_baseline and world == 1:
             ref, src, dmin, dmax = problem(0)[1]
             cw, ch = [int(x) for x in a.cpu_crop.split("x")]
             host_views = [syn.View(K, R, T, g.cpu().numpy(), None, None) for (K, R, T, g, _, _) in views]
             out["cpu_baseline"] = cpu_baseline(host_views, ref, src, dmin, dmax, (cw, ch))
             if a.reference_build:
                 out["reference_hip_build"] = reference_build_leg(host_views, ref, src, dmin, dmax, (cw, ch))
-        if not a.no_dropin and world == 1:
+        if a.full and not a.no_dropin and world == 1:
             out["dropin"] = dropin_leg(a, problem, value)
-        if not a.no_geom and world == 1:
+        if a.full and not a.no_geom and world == 1:
             fmaps, out["geometric"] = geometric_leg(a, views, images, cache, local_rank)
             if fmaps:
                 mvs.release_cached_memory()
                 out["fusion"] = fusion_leg(a, views, fmaps, not a.no_cpu_baseline)
-        if not a.no_ba and world == 1:
+        if a.full and not a.no_ba and world == 1:
             del pms_keepalive[:]
             torch.cuda.empty_cache()
             mvs.release_cached_memory()
             out["secondary"] = ba_secondary(a, local_rank, not a.no_cpu_baseline)
-    # N > 1: the secondary (bundle adjustment) leg is ONE solve sharded over all ranks
-    if not a.no_ba and world > 1:
+    # N > 1 with --full: the secondary (bundle adjustment) leg is ONE solve sharded over all ranks
+    if a.full and not a.no_ba and world > 1:
         torch.cuda.empty_cache()
         mvs.release_cached_memory()
         # The sharded BA leg is the only part of this script with data-path collectives. The primary

@@ -19,7 +19,9 @@ fi
 out=${HIP_EMUL_ASAN_DIR:-$(mktemp -d)}
 export HIP_EMUL_ASAN_DIR="$out"
 printf 'extern "C" void pm_release_cached_memory(void) {}\n' > "$out/stubs.cpp"
-ln -sf "$root/colmap_amd/csrc/pm_kernels.hip" "$here/pm/pm_kernels.hip"
+mkdir -p "$out/pm"   # pm_kernels.hip through a link next to the stand-in's gfx950/ (see build_pm.sh)
+ln -sf "$root/colmap_amd/csrc/pm_kernels.hip" "$out/pm/pm_kernels.hip"
+ln -sfn "$here/pm/gfx950" "$out/pm/gfx950"
 F="-O1 -g $san -fno-omit-frame-pointer -std=c++17 -fPIC -shared -mavx2 -mfma -ffp-contract=off -Wno-unknown-attributes"
 "$cxx" $F -fvisibility=hidden -I "$here" -x c++ "$root/colmap_amd/csrc/fusion.hip" "$out/stubs.cpp" -o "$out/libfusion_asan.so" &
 p1=$!
@@ -29,7 +31,7 @@ p2=$!
 "$cxx" $F -fvisibility-inlines-hidden -Wl,-Bsymbolic -I "$here" -I "$root/colmap_amd/csrc" -x c++ "$root/colmap_amd/csrc/ba_kernels.hip" \
     "$root/colmap_amd/csrc/ba_schur_explicit.hip" "$out/stubs.cpp" -o "$out/libba_asan.so" &
 p3=$!
-"$cxx" $F -fvisibility-inlines-hidden -Wl,-Bsymbolic -I "$here" -I "$root/colmap_amd/csrc" -x c++ "$here/pm/pm_kernels.hip" \
+"$cxx" $F -fvisibility-inlines-hidden -Wl,-Bsymbolic -I "$here" -I "$root/colmap_amd/csrc" -x c++ "$out/pm/pm_kernels.hip" \
     "$root/colmap_amd/csrc/pm_api.cpp" "$here/pm/pm_stubs.cpp" -o "$out/libpm_asan.so" &
 p4=$!
 wait $p1; wait $p2; wait $p3; wait $p4
