@@ -27,6 +27,7 @@
 //    Gram tile).
 //  * S x = (B + D^2) x - E C^-1 E^T x is never formed: three kernels per product.
 #include "../../include/colmap_amd_ba.h"
+#include "../../include/colmap_amd_ba_covariance.h"
 #include "ba_schur_explicit.h"
 #include "switches.h"
 
@@ -40,6 +41,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <numeric>
 #include <stdexcept>
 #include <thread>
@@ -4626,7 +4628,252 @@ struct Solver {
   }
 };
 
+// ------------------------------------------------------------------------------------------
+// Covariance estimation (include/colmap_amd_ba_covariance.h)
+// ------------------------------------------------------------------------------------------
+
+// One pass over the points: the damped, scaled C^-1 = (E_s^T E_s + damping s_p^2)^-1 the formation reads (no LM
+// diagonal), and the unscaled covariance s_p C^-1 s_p = (E^T E + damping I)^-1 (row-major 3 x 3 per point).
+__global__ void ba_cov_point_kernel(View V, const double* __restrict__ Craw, double damping, double* __restrict__ Cinv,
+                                    double* __restrict__ cov) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= V.n_points) return;
+  const int off = V.pt_off[j];
+  if (off < 0) return;
+  const double s[3] = {V.scale_p[off], V.scale_p[off + 1], V.scale_p[off + 2]};
+  double C[6];
+  for (int e = 0; e < 6; ++e) C[e] = Craw[(size_t)e * V.n_points + j];
+  C[0] += damping * s[0] * s[0];
+  C[3] += damping * s[1] * s[1];
+  C[5] += damping * s[2] * s[2];
+  const double a = C[0], b = C[1], c = C[2], d = C[3], e = C[4], f = C[5];
+  const double A = d * f - e * e, B = c * e - b * f, Cc = b * e - c * d;
+  const double id = 1.0 / (a * A + b * B + c * Cc);
+  const double m[9] = {A * id, B * id, Cc * id, B * id, (a * f - c * c) * id, (b * c - a * e) * id,
+                       Cc * id, (b * c - a * e) * id, (a * d - b * b) * id};
+  double* out = Cinv + 9 * (size_t)j;
+  double* cv = cov + 9 * (size_t)j;
+  for (int r = 0; r < 3; ++r)
+    for (int q = 0; q < 3; ++q) {
+      out[3 * r + q] = m[3 * r + q];
+      cv[3 * r + q] = s[r] * m[3 * r + q] * s[q];
+    }
+}
+
+// Diagonal of the covariance system before the factorisation: rows [0, n_o) are the others (+ damping s^2 when they are
+// eliminated, damp_o = 0 with BA_COV_ALL), rows [n_o, n_op) the identity rows that pad them to a multiple of 64.
+__global__ void ba_cov_diag_kernel(double* __restrict__ S, int n, int n_o, int n_op, double damp_o,
+                                   const double* __restrict__ scale) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_op) return;
+  double* d = S + (size_t)i * n + i;
+  if (i >= n_o) *d = 1.0;
+  else *d += damp_o * scale[i] * scale[i];
+}
+
+// Pivots of the factorisation in unscaled units: d_i = (L_ii / s_i)^2.
+__global__ void ba_cov_pivot_kernel(const double* __restrict__ S, int n, const double* __restrict__ scale,
+                                    double* __restrict__ d) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double l = S[(size_t)i * n + i] / scale[i];
+  d[i] = l * l;
+}
+
+struct CovHandle {
+  int device = 0;
+  int mode = BA_COV_ALL;
+  int n = 0, n_o = 0, n_op = 0;  // factored dimension; others and their padded width (the poses start at n_op)
+  int j0 = 0;                    // first 64-block column of X that was inverted
+  double* X = nullptr;           // rows / columns [64 j0, n) of L^-1 (device, (n - 64 j0)^2), lower triangular
+  double* scale = nullptr;       // [n] Jacobi scales of the rows of X (device; 1 on the padding)
+  hipStream_t st = nullptr;
+  hipEvent_t ev_a = nullptr, ev_b = nullptr;
+  std::vector<int> pose_off, pose_dim, cam_off, cam_dim, sens_off, sens_dim;  // offsets in X, -1: no result
+  std::vector<double> point_cov;  // [num_points][9]
+  std::vector<char> point_has;
+  double form_ms = 0.0, factor_ms = 0.0, inverse_ms = 0.0, extract_ms = 0.0;
+  ~CovHandle() {
+    if (X) (void)hipFree(X);
+    if (scale) (void)hipFree(scale);
+    if (ev_a) (void)hipEventDestroy(ev_a);
+    if (ev_b) (void)hipEventDestroy(ev_b);
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
+double elapsed_ms(hipEvent_t a, hipEvent_t b) {
+  BA_HIP(hipEventSynchronize(b));
+  float ms = 0.f;
+  BA_HIP(hipEventElapsedTime(&ms, a, b));
+  return ms;
+}
+
+// Sets up the solver's linearisation at the current parameters (Jacobi scales from the same Jacobian, as the LM loop's
+// first iteration), then points, formation, factorisation and triangular inverse. Returns BA_COV_OK or
+// BA_COV_NOT_ESTIMABLE (g_ba_error holds the message); throws on errors.
+int estimate_covariance(Solver& s, const ba_covariance_options& co, CovHandle& h) {
+  const ba_problem& p = s.prob;
+  h.mode = co.params;
+  h.pose_off.assign(p.num_poses, -1); h.pose_dim.assign(p.num_poses, 0);
+  h.cam_off.assign(p.num_cams, -1); h.cam_dim.assign(p.num_cams, 0);
+  h.sens_off.assign(std::max(p.num_sensors, 0), -1); h.sens_dim.assign(std::max(p.num_sensors, 0), 0);
+  h.point_cov.assign(9 * (size_t)std::max(p.num_points, 0), 0.0);
+  h.point_has.assign(std::max(p.num_points, 0), 0);
+  BA_HIP(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
+  for (hipEvent_t* e : {&s.ev0, &s.ev1, &s.ev2, &s.ev3}) BA_HIP(hipEventCreate(e));
+  ba_result dummy{};
+  if (s.build(&dummy) == 0) return BA_COV_OK;  // no variable block is observed: every query has no result
+  View& V = s.V;
+  const int nc = V.n_c, np = V.n_p;
+  const hipStream_t st = s.st;
+  BA_LAUNCH(ba_scale_kernel, dim3(std::max(grid_for(nc, 256), 1)), dim3(256), st, nc, s.diag_c.p, 0, s.scale_c.p);
+  BA_LAUNCH(ba_scale_kernel, dim3(std::max(grid_for(np, 256), 1)), dim3(256), st, np, s.diag_p.p, 0, s.scale_p.p);
+  s.launch_linearize(true, s.poses.p, s.cams.p, s.points.p, s.sensors.p, S_COST);
+  s.gradient_and_diag();
+  BA_LAUNCH(ba_scale_kernel, dim3(std::max(grid_for(nc, 256), 1)), dim3(256), st, nc, s.diag_c.p, s.opt.jacobi_scaling, s.scale_c.p);
+  BA_LAUNCH(ba_scale_kernel, dim3(std::max(grid_for(np, 256), 1)), dim3(256), st, np, s.diag_p.p, s.opt.jacobi_scaling, s.scale_p.p);
+  s.launch_linearize(true, s.poses.p, s.cams.p, s.points.p, s.sensors.p, S_COST);
+  s.gradient_and_diag();
+  // 1. points
+  Buf<double> pcov;
+  pcov.alloc(9 * (size_t)std::max(p.num_points, 1));
+  if (p.num_points > 0)
+    BA_LAUNCH(ba_cov_point_kernel, dim3(grid_for(p.num_points, 128)), dim3(128), st, V, s.Craw.p, co.damping, s.Cinv.p, pcov.p);
+  if (co.params != BA_COV_POSES) {
+    BA_HIP(hipMemcpyAsync(h.point_cov.data(), pcov.p, sizeof(double) * h.point_cov.size(), hipMemcpyDeviceToHost, st));
+    BA_HIP(hipStreamSynchronize(st));
+    for (int j = 0; j < p.num_points; ++j) h.point_has[j] = s.h_pt_off[j] >= 0;
+  }
+  if (co.params == BA_COV_POINTS || nc == 0) return BA_COV_OK;
+  // 2. the camera-side order of the covariance system: others (intrinsics, then sensor_from_rig blocks, in the solver's
+  // order) padded with identity rows to a multiple of 64, then the poses
+  std::vector<int> pdim(p.num_poses, 0), cdim(p.num_cams, 0);
+  BA_HIP(hipMemcpy(pdim.data(), s.pose_dim.p, sizeof(int) * pdim.size(), hipMemcpyDeviceToHost));
+  BA_HIP(hipMemcpy(cdim.data(), s.cam_dim.p, sizeof(int) * cdim.size(), hipMemcpyDeviceToHost));
+  int n_pd = 0;
+  for (int i = 0; i < p.num_poses; ++i) n_pd += s.h_pose_off[i] >= 0 ? pdim[i] : 0;
+  const int n_o = nc - n_pd;  // the solver's layout: poses [0, n_pd), then intrinsics and sensors
+  const int n_op = (n_o + 63) / 64 * 64;
+  const int n = n_op + n_pd;
+  if (n > 32768)
+    throw std::runtime_error("covariance: camera-side dimension " + std::to_string(n) + " exceeds the limit of 32768");
+  auto remap = [&](int off) { return off < 0 ? -1 : (off < n_pd ? off + n_op : off - n_pd); };
+  std::vector<int> npose(p.num_poses), ncam(p.num_cams), nsens(s.h_sens_off.size());
+  for (int i = 0; i < p.num_poses; ++i) npose[i] = remap(s.h_pose_off[i]);
+  for (int k = 0; k < p.num_cams; ++k) ncam[k] = remap(s.h_cam_off[k]);
+  for (size_t k = 0; k < nsens.size(); ++k) nsens[k] = remap(s.h_sens_off[k]);
+  std::vector<double> sc_old(std::max(nc, 1)), sc(n, 1.0);
+  BA_HIP(hipMemcpyAsync(sc_old.data(), s.scale_c.p, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
+  BA_HIP(hipStreamSynchronize(st));
+  for (int i = 0; i < nc; ++i) sc[remap(i)] = sc_old[i];
+  Buf<int> d_pose, d_cam, d_sens, d_po, d_so;
+  d_pose.upload(npose); d_cam.upload(ncam);
+  if (!nsens.empty()) d_sens.upload(nsens);
+  BA_HIP(hipMalloc(reinterpret_cast<void**>(&h.scale), sizeof(double) * n));
+  BA_HIP(hipMemcpy(h.scale, sc.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+  if (s.use_priors()) {
+    std::vector<int> po(s.Q.n), so(s.Q.n);
+    BA_HIP(hipMemcpy(po.data(), s.Q.po, sizeof(int) * s.Q.n, hipMemcpyDeviceToHost));
+    BA_HIP(hipMemcpy(so.data(), s.Q.so, sizeof(int) * s.Q.n, hipMemcpyDeviceToHost));
+    for (int k = 0; k < s.Q.n; ++k) { po[k] = remap(po[k]); so[k] = remap(so[k]); }
+    d_po.upload(po); d_so.upload(so);
+  }
+  BA_HIP(hipDeviceSynchronize());  // (uploads on the NULL stream)
+  s.chol_info.alloc(2);
+  ba_explicit::FormArgs fa = s.form_args();
+  fa.n_c = n;
+  fa.pose_off = d_pose.p; fa.cam_off = d_cam.p;
+  fa.sens_off = V.sens_off ? d_sens.p : nullptr;
+  if (dev_switch_int("COLMAP_AMD_BA_FORM_PAIRS", 1) != 0 && ba_explicit::build_pair_lists(fa, s.pair_lists, st))
+    fa.pairs = &s.pair_lists;
+  s.Sdense.alloc((size_t)n * n + n);
+  ba_explicit::Workspace ws;
+  s.chol_linv.alloc(ws.linv_doubles(n)); s.chol_tmp.alloc(n);
+  Buf<double> zrhs, xsol, piv;
+  zrhs.alloc(n); xsol.alloc(n); piv.alloc(n);
+  BA_HIP(hipDeviceSynchronize());
+  BA_HIP(hipEventRecord(s.ev2, st));
+  ba_explicit::form(fa, s.Sdense.p, st);
+  if (s.use_priors())
+    ba_explicit::add_prior_rows(s.Sdense.p, n, s.Q.J, d_po.p, d_so.p, s.Q.pdim, s.Q.n, fa.fixed_point, fa.bad, st);
+  ba_explicit::finish(s.Sdense.p, n, fa.fixed_point, fa.bad, st);
+  if (n_op > 0)
+    BA_LAUNCH(ba_cov_diag_kernel, dim3(grid_for(n_op, 256)), dim3(256), st, s.Sdense.p, n, n_o, n_op,
+              co.params == BA_COV_ALL ? 0.0 : co.damping, h.scale);
+  BA_HIP(hipEventRecord(s.ev3, st));
+  // 3. factorisation (the right-hand side is zero; its solution is not used)
+  ws.Linv = s.chol_linv.p; ws.tmp = s.chol_tmp.p; ws.info = s.chol_info.p;
+  if (dev_switch_int("COLMAP_AMD_BA_CHOL_LOOKAHEAD", 1) != 0) {
+    int prio_least = 0, prio_greatest = 0;
+    BA_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    BA_HIP(hipStreamCreateWithPriority(&s.st_chol, hipStreamNonBlocking, prio_least));
+    BA_HIP(hipEventCreateWithFlags(&s.ev_chol_panel, hipEventDisableTiming));
+    BA_HIP(hipEventCreateWithFlags(&s.ev_chol_u2, hipEventDisableTiming));
+    ws.st2 = s.st_chol; ws.ev_panel = s.ev_chol_panel; ws.ev_u2 = s.ev_chol_u2;
+  }
+  double fms = 0.0;
+  ba_explicit::factor_solve(s.Sdense.p, n, zrhs.p, xsol.p, ws, st, s.ev0, s.ev1, &fms);
+  h.form_ms = elapsed_ms(s.ev2, s.ev3);
+  h.factor_ms = fms;
+  BA_LAUNCH(ba_cov_pivot_kernel, dim3(grid_for(n, 256)), dim3(256), st, s.Sdense.p, n, h.scale, piv.p);
+  std::vector<double> d(n);
+  int info[2] = {0, 0};
+  BA_HIP(hipMemcpyAsync(d.data(), piv.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  BA_HIP(hipMemcpyAsync(info, s.chol_info.p, sizeof(info), hipMemcpyDeviceToHost, st));
+  BA_HIP(hipStreamSynchronize(st));
+  // 4. rank: the columns of the matrix whose inverse is returned (with eliminated others, the poses only)
+  int cols = 0, rank = 0;
+  for (int i = 0; i < n; ++i) {
+    const bool counted = i >= n_op || (co.params == BA_COV_ALL && i < n_o);
+    if (!counted) continue;
+    ++cols;
+    rank += d[i] > 1e-6 ? 1 : 0;  // (a NaN pivot is not counted)
+  }
+  const bool failed = info[0] != 0;  // a pivot that was not positive (the others' block included)
+  if (failed && cols > 0 && rank == cols) --rank;
+  if (failed || rank < cols) {
+    g_ba_error = "Unable to compute covariance. The Schur complement on pose/other parameters is rank deficient. "
+                 "Number of columns: " + std::to_string(cols) + ", rank: " + std::to_string(rank) +
+                 ". This is likely due to the pose/other parameters being underconstrained with Gauge ambiguity or "
+                 "other degeneracies.";
+    return BA_COV_NOT_ESTIMABLE;
+  }
+  // 5. X = L^-1 (only the poses' block columns when the others were eliminated)
+  h.n = n; h.n_o = n_o; h.n_op = n_op;
+  h.j0 = co.params == BA_COV_ALL ? 0 : n_op / 64;
+  const size_t nx = (size_t)(n - 64 * h.j0);  // only the inverted trailing part is stored
+  BA_HIP(hipMalloc(reinterpret_cast<void**>(&h.X), sizeof(double) * std::max<size_t>(nx * nx, 1)));
+  BA_HIP(hipEventRecord(s.ev2, st));
+  ba_explicit::tri_inverse(s.Sdense.p, n, h.j0, s.chol_linv.p, h.X, st);
+  BA_HIP(hipEventRecord(s.ev3, st));
+  h.inverse_ms = elapsed_ms(s.ev2, s.ev3);
+  for (int i = 0; i < p.num_poses; ++i)
+    if (npose[i] >= 0) { h.pose_off[i] = npose[i]; h.pose_dim[i] = pdim[i]; }
+  if (co.params == BA_COV_ALL) {
+    for (int k = 0; k < p.num_cams; ++k)
+      if (ncam[k] >= 0) { h.cam_off[k] = ncam[k]; h.cam_dim[k] = cdim[k]; }
+    for (size_t k = 0; k < nsens.size(); ++k)
+      if (nsens[k] >= 0) { h.sens_off[k] = nsens[k]; h.sens_dim[k] = 6; }
+  }
+  return BA_COV_OK;
+}
+
+bool cov_block(const CovHandle& h, int kind, int index, int* off, int* dim) {
+  const std::vector<int>* o = kind == BA_COV_KIND_POSE ? &h.pose_off : kind == BA_COV_KIND_CAMERA ? &h.cam_off
+                            : kind == BA_COV_KIND_SENSOR ? &h.sens_off : nullptr;
+  const std::vector<int>* d = kind == BA_COV_KIND_POSE ? &h.pose_dim : kind == BA_COV_KIND_CAMERA ? &h.cam_dim : &h.sens_dim;
+  if (!o || index < 0 || index >= (int)o->size() || (*o)[index] < 0) return false;
+  *off = (*o)[index];
+  *dim = (*d)[index];
+  return true;
+}
+
 }  // namespace
+
+struct ba_covariance {
+  CovHandle h;
+};
 
 extern "C" {
 
@@ -4773,6 +5020,128 @@ int ba_last_spmv_timing(double* total_ms, int64_t* launches, int64_t* bytes_per_
   if (launches) *launches = g_spmv_launches;
   if (bytes_per_launch) *bytes_per_launch = g_spmv_bytes;
   return 0;
+}
+
+void ba_covariance_options_init(ba_covariance_options* o) {
+  std::memset(o, 0, sizeof(*o));
+  o->params = BA_COV_ALL;  // BACovarianceOptions (covariance.h)
+  o->damping = 1e-8;
+}
+
+int ba_estimate_covariance(const ba_problem* problem, const ba_options* options, const ba_covariance_options* cov_options,
+                           int32_t gpu_index, ba_covariance** out) {
+  if (out) *out = nullptr;
+  try {
+    if (!problem || !options || !cov_options || !out) throw std::runtime_error("null argument");
+    if (cov_options->params < BA_COV_POSES || cov_options->params > BA_COV_ALL)
+      throw std::runtime_error("ba_covariance_options.params");
+    if (!(cov_options->damping >= 0.0)) throw std::runtime_error("ba_covariance_options.damping must be >= 0");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+      throw std::runtime_error("no HIP device available: the MI355X bundle-adjustment backend has no CPU fallback");
+    if (gpu_index >= ndev) throw std::runtime_error("gpu_index out of range");
+    if (gpu_index >= 0) BA_HIP(hipSetDevice(gpu_index));
+    auto cov = std::make_unique<ba_covariance>();
+    CovHandle& h = cov->h;
+    BA_HIP(hipGetDevice(&h.device));
+    int rc;
+    {
+      Comm comm;
+      // the solver only reads the problem here: it uploads copies and never writes back
+      Solver s(*const_cast<ba_problem*>(problem), *options, comm);
+      rc = estimate_covariance(s, *cov_options, h);
+    }
+    if (rc != BA_COV_OK) return rc;
+    BA_HIP(hipStreamCreateWithFlags(&h.st, hipStreamNonBlocking));
+    BA_HIP(hipEventCreate(&h.ev_a));
+    BA_HIP(hipEventCreate(&h.ev_b));
+    *out = cov.release();
+    return BA_COV_OK;
+  } catch (const std::exception& e) {
+    g_ba_error = e.what();
+    return BA_COV_ERROR;
+  }
+}
+
+int ba_covariance_block_dim(const ba_covariance* cov, int32_t kind, int32_t index, int32_t* dim) {
+  if (!cov || !dim) return BA_COV_ERROR;
+  int off = 0, d = 0;
+  *dim = cov_block(cov->h, kind, index, &off, &d) ? d : 0;
+  return *dim > 0 ? BA_COV_OK : BA_COV_NO_RESULT;
+}
+
+int ba_covariance_point(const ba_covariance* cov, int32_t index, double out[9]) {
+  if (!cov || !out) return BA_COV_ERROR;
+  const CovHandle& h = cov->h;
+  if (index < 0 || index >= (int)h.point_has.size() || !h.point_has[index]) return BA_COV_NO_RESULT;
+  std::memcpy(out, h.point_cov.data() + 9 * (size_t)index, 9 * sizeof(double));
+  return BA_COV_OK;
+}
+
+int ba_covariance_blocks(ba_covariance* cov, int32_t count, const ba_covariance_pair* pairs, double* out, int32_t* found) {
+  try {
+    if (!cov || count < 0 || (count > 0 && (!pairs || !out || !found))) throw std::runtime_error("null argument");
+    CovHandle& h = cov->h;
+    std::vector<ba_explicit::CovPair> req;
+    std::vector<int> slot;
+    for (int k = 0; k < count; ++k) {
+      ba_explicit::CovPair cp{};
+      const bool ok = h.X && cov_block(h, pairs[k].kind_a, pairs[k].index_a, &cp.a0, &cp.da) &&
+                      cov_block(h, pairs[k].kind_b, pairs[k].index_b, &cp.b0, &cp.db);
+      found[k] = ok ? 1 : 0;
+      if (ok) {
+        cp.a0 -= 64 * h.j0;
+        cp.b0 -= 64 * h.j0;
+        const int nx = h.n - 64 * h.j0;
+        if (cp.a0 < 0 || cp.b0 < 0 || cp.a0 + cp.da > nx || cp.b0 + cp.db > nx || cp.da > 16 || cp.db > 16)
+          throw std::runtime_error("covariance: block outside the inverted part");
+        req.push_back(cp);
+        slot.push_back(k);
+      }
+    }
+    if (req.empty()) return BA_COV_OK;
+    BA_HIP(hipSetDevice(h.device));
+    Buf<ba_explicit::CovPair> dpairs;
+    Buf<double> dout;
+    dpairs.upload(req);
+    dout.alloc(req.size() * ba_explicit::kCovSlot);
+    BA_HIP(hipDeviceSynchronize());  // (uploads on the NULL stream)
+    BA_HIP(hipEventRecord(h.ev_a, h.st));
+    const int xo = 64 * h.j0;  // X's first row / column (the pose blocks queried lie beyond it)
+    ba_explicit::extract_cov_blocks(h.X, h.n - xo, dpairs.p, (int)req.size(), h.scale + xo, dout.p, h.st);
+    BA_HIP(hipGetLastError());
+    BA_HIP(hipEventRecord(h.ev_b, h.st));
+    std::vector<double> hout(dout.n);
+    BA_HIP(hipMemcpyAsync(hout.data(), dout.p, sizeof(double) * dout.n, hipMemcpyDeviceToHost, h.st));
+    BA_HIP(hipStreamSynchronize(h.st));
+    h.extract_ms = elapsed_ms(h.ev_a, h.ev_b);
+    for (size_t q = 0; q < req.size(); ++q)
+      std::memcpy(out + (size_t)slot[q] * BA_COV_SLOT, hout.data() + q * ba_explicit::kCovSlot,
+                  sizeof(double) * req[q].da * req[q].db);
+    return BA_COV_OK;
+  } catch (const std::exception& e) {
+    g_ba_error = e.what();
+    return BA_COV_ERROR;
+  }
+}
+
+int ba_covariance_timing(const ba_covariance* cov, double* form_ms, double* factor_ms, double* inverse_ms,
+                         double* extract_ms, int32_t* n, int32_t* n_inv) {
+  if (!cov) return BA_COV_ERROR;
+  const CovHandle& h = cov->h;
+  if (form_ms) *form_ms = h.form_ms;
+  if (factor_ms) *factor_ms = h.factor_ms;
+  if (inverse_ms) *inverse_ms = h.inverse_ms;
+  if (extract_ms) *extract_ms = h.extract_ms;
+  if (n) *n = h.n;
+  if (n_inv) *n_inv = std::max(h.n - 64 * h.j0, 0);
+  return BA_COV_OK;
+}
+
+void ba_covariance_destroy(ba_covariance* cov) {
+  if (!cov) return;
+  (void)hipSetDevice(cov->h.device);
+  delete cov;
 }
 
 const char* ba_last_error(void) { return g_ba_error.c_str(); }

@@ -94,4 +94,16 @@ struct Workspace {
 void factor_solve(double* S, int n, const double* rhs, double* x, const Workspace& ws, hipStream_t st,
                   hipEvent_t ev_a, hipEvent_t ev_b, double* mfma_ms);
 
+// Covariance (ba_estimate_covariance). After factor_solve: X = the trailing part (rows and columns [64 j0, n)) of L^-1,
+// (n - 64 j0)^2 doubles, row-major, cleared inside -- L^-1 of the trailing block of L -- one launch per block row on the
+// f64 matrix cores, starting from the stored inverses of the diagonal blocks (ws.Linv). About (n - 64 j0)^3 / 3 flop.
+void tri_inverse(const double* L, int n, int j0, const double* Linv, double* X, hipStream_t st);
+// Blocks of X^T X: pair k -> out[k * kCovSlot ...] = row-major (da x db) block s_a (X^T X)_ab s_b, one launch.
+constexpr int kCovSlot = 256;  // doubles per result slot: the widest block is 16 (RAD_TAN_THIN_PRISM_FISHEYE intrinsics)
+struct CovPair {
+  int a0, da, b0, db;  // first row / column and width of the two blocks in X's coordinates
+};
+void extract_cov_blocks(const double* X, int n, const CovPair* pairs /* device */, int count, const double* scale,
+                        double* out, hipStream_t st);
+
 }  // namespace ba_explicit

@@ -1117,7 +1117,139 @@ __global__ void nan_fill_kernel(int n, const int* __restrict__ info, double* __r
   if (i < n && *info != 0) x[i] = NAN;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Covariance: X = L^-1 and blocks of X^T X
+// ---------------------------------------------------------------------------------------------------------
+
+// Block row i of X = L^-1 (64-blocks; L lower, row-major in S with row stride n):
+//     X_ii = Linv_i,    X_ij = -Linv_i sum_{k=j}^{i-1} L_ik X_kj    (j0 <= j < i).
+// Workgroup b handles block column j = j0 + b; the last one (j == i) copies the stored inverse of the diagonal block.
+// Every X_kj it reads (k < i) was written by an earlier launch. The 64 x 64 sum runs on the matrix cores with the
+// operand layout of chol_panel_kernel (wave w: rows 16 w .. 16 w + 15, four 16 x 16 tiles), K streamed in 64-blocks
+// through LDS; then T goes back through LDS and is multiplied by -Linv_i. Blocks below the last row of L (a short last
+// block row) read zeros and are not stored.
+__global__ void __launch_bounds__(256) tri_inv_row_kernel(const double* __restrict__ L, double* __restrict__ X, int n, int i,
+                                                          int j0, const double* __restrict__ Linv) {
+  // X holds rows / columns [64 j0, n) only: entry (r, c) at (r - xo) * ldx + c - xo
+  const int xo = NB * j0, ldx = n - xo;
+  __shared__ double sA[NB][NB + 1];
+  __shared__ double sB[NB][NB + 1];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 15, lk = lane >> 4;
+  const int j = j0 + blockIdx.x;
+  const int r0 = NB * i, c0 = NB * j;
+  const int nr = min(NB, n - r0);
+  const double* Li = Linv + (size_t)i * NB * NB;
+  if (j == i) {
+    for (int e = tid; e < NB * NB; e += 256) {
+      const int r = e >> 6, c = e & 63;
+      if (r < nr && c < nr) X[(size_t)(r0 + r - xo) * ldx + r0 + c - xo] = Li[e];
+    }
+    return;
+  }
+  const int c = tid & 63, rq = tid >> 6;
+  v4f64 acc[4];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) acc[ct] = v4f64{0.0, 0.0, 0.0, 0.0};
+  for (int k0 = c0; k0 < r0; k0 += NB) {  // (k0 + 64 <= r0 <= n: every K block is whole, and so is block column j)
+    double va[16], vb[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int r = rq + 4 * q;
+      va[q] = r < nr ? L[(size_t)(r0 + r) * n + k0 + c] : 0.0;
+      vb[q] = X[(size_t)(k0 + r - xo) * ldx + c0 + c - xo];
+    }
+    __syncthreads();  // the previous block's readers are done
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      sA[rq + 4 * q][c] = va[q];
+      sB[rq + 4 * q][c] = vb[q];
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int ks = 0; ks < NB / 4; ++ks) {
+      const int m = 4 * ks + lk;
+      const double a = sA[16 * wave + li][m];
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sB[m][16 * ct + li], acc[ct], 0, 0, 0);
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) sA[16 * wave + lk + 4 * reg][16 * ct + li] = acc[ct][reg];  // T
+  {
+    double vl[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) vl[q] = Li[(rq + 4 * q) * NB + c];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sB[rq + 4 * q][c] = vl[q];  // Linv_i
+  }
+  __syncthreads();
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) acc[ct] = v4f64{0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+  for (int ks = 0; ks < NB / 4; ++ks) {
+    const int m = 4 * ks + lk;
+    const double a = -sB[16 * wave + li][m];
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sA[m][16 * ct + li], acc[ct], 0, 0, 0);
+  }
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int r = 16 * wave + lk + 4 * reg;
+      if (r < nr) X[(size_t)(r0 + r - xo) * ldx + c0 + 16 * ct + li - xo] = acc[ct][reg];
+    }
+}
+
+// One workgroup per requested pair (a, b): out[pair][e] = s_a X[:, a]^T X[:, b] s_b, e = row-major (da x db) entry,
+// over the rows >= max(a0, b0) (X is lower triangular). Wave w sums the rows r = w (mod 4), lane = entries
+// e = lane + 64 q; the four wave partials are added in a fixed order: bit-reproducible.
+__global__ void __launch_bounds__(256) cov_extract_kernel(const double* __restrict__ X, int n, const CovPair* __restrict__ pairs,
+                                                          const double* __restrict__ scale, double* __restrict__ out) {
+  __shared__ double part[4][kCovSlot];
+  const CovPair pr = pairs[blockIdx.x];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int E = pr.da * pr.db;
+  int ea[4], eb[4];
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int e = min(lane + 64 * q, E - 1);  // (lanes beyond E repeat the last entry; their sums are not stored)
+    ea[q] = pr.a0 + e / pr.db;
+    eb[q] = pr.b0 + e % pr.db;
+  }
+  for (int r = max(pr.a0, pr.b0) + wave; r < n; r += 4) {
+    const double* row = X + (size_t)r * n;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q] = fma(row[ea[q]], row[eb[q]], acc[q]);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) part[wave][lane + 64 * q] = acc[q];
+  __syncthreads();
+  for (int e = tid; e < E; e += 256) {
+    const int a = pr.a0 + e / pr.db, b = pr.b0 + e % pr.db;
+    out[(size_t)blockIdx.x * kCovSlot + e] = scale[a] * ((part[0][e] + part[1][e]) + (part[2][e] + part[3][e])) * scale[b];
+  }
+}
+
 }  // namespace
+
+void tri_inverse(const double* L, int n, int j0, const double* Linv, double* X, hipStream_t st) {
+  const size_t nx = (size_t)std::max(n - NB * j0, 0);
+  BAX_HIP(hipMemsetAsync(X, 0, nx * nx * sizeof(double), st));
+  const int nb = (n + NB - 1) / NB;
+  for (int i = j0; i < nb; ++i)
+    hipLaunchKernelGGL(tri_inv_row_kernel, dim3(i - j0 + 1), dim3(256), 0, st, L, X, n, i, j0, Linv);
+}
+
+void extract_cov_blocks(const double* X, int n, const CovPair* pairs, int count, const double* scale, double* out,
+                        hipStream_t st) {
+  if (count > 0) hipLaunchKernelGGL(cov_extract_kernel, dim3(count), dim3(256), 0, st, X, n, pairs, scale, out);
+}
 
 void form(const FormArgs& a, double* S, hipStream_t st) {
   const size_t n = (size_t)a.n_c;

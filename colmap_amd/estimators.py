@@ -1116,3 +1116,217 @@ def CreateDefaultBundleAdjuster(options: BundleAdjustmentOptions, config: Bundle
         raise ValueError(f"backend {options.backend!r} is not built here: only MI355X "
                          "(the reference's CERES/CASPAR need Ceres/CUDA)")
     return BundleAdjuster(options, config, reconstruction)
+
+
+# ---------------------------------------------------------------------------------------------
+# Covariance of the bundle-adjustment result (reference estimators/covariance.h: BACovarianceOptions,
+# BACovariance, EstimateBACovariance) over include/colmap_amd_ba_covariance.h
+# ---------------------------------------------------------------------------------------------
+
+class BACovarianceParams(enum.IntEnum):
+    """BACovarianceOptions::Params"""
+    POSES = 0
+    POINTS = 1
+    POSES_AND_POINTS = 2
+    ALL = 3
+
+
+@dataclass
+class BACovarianceOptions:
+    Params = BACovarianceParams
+    params: BACovarianceParams = BACovarianceParams.ALL
+    damping: float = 1e-8
+
+
+COV_OK, COV_ERROR, COV_NOT_ESTIMABLE, COV_NO_RESULT = 0, 1, 2, 3
+COV_KIND_POSE, COV_KIND_CAMERA, COV_KIND_SENSOR = 0, 1, 2
+COV_SLOT = 256  # BA_COV_SLOT
+
+
+class ba_covariance_options(C.Structure):
+    _fields_ = [("params", C.c_int32), ("damping", C.c_double)]
+
+
+class ba_covariance_pair(C.Structure):
+    _fields_ = [("kind_a", C.c_int32), ("index_a", C.c_int32), ("kind_b", C.c_int32), ("index_b", C.c_int32)]
+
+
+def _cov_prototypes(L):
+    L.ba_estimate_covariance.restype = C.c_int
+    L.ba_estimate_covariance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+    L.ba_covariance_block_dim.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+    L.ba_covariance_point.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.ba_covariance_blocks.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ba_covariance_timing.argtypes = [C.c_void_p] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int32)] * 2
+    L.ba_covariance_destroy.argtypes = [C.c_void_p]
+    L.ba_covariance_destroy.restype = None
+
+
+class FlatCovariance:
+    """Result of ba_estimate_covariance on a flat problem: blocks are addressed by their slot in the problem's arrays
+    (pose / camera / sensor index, point index). Owns the device copy of L^-1 until close()."""
+
+    def __init__(self, L, handle: C.c_void_p, num_points: int):
+        self._L = L
+        self._h = handle
+        self.num_points = num_points
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            self._L.ba_covariance_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError("the covariance handle was closed")
+        return self._h
+
+    def block_dim(self, kind: int, index: int) -> int:
+        d = C.c_int32(0)
+        self._L.ba_covariance_block_dim(self._handle(), kind, index, C.byref(d))
+        return int(d.value)
+
+    def point(self, index: int) -> Optional[np.ndarray]:
+        out = np.zeros(9)
+        rc = self._L.ba_covariance_point(self._handle(), index, out.ctypes.data)
+        return out.reshape(3, 3) if rc == COV_OK else None
+
+    def blocks(self, pairs: Sequence[tuple]) -> List[Optional[np.ndarray]]:
+        """[(kind_a, index_a, kind_b, index_b), ...] -> cross covariances (None: a block has no result); one launch."""
+        n = len(pairs)
+        if n == 0:
+            return []
+        req = (ba_covariance_pair * n)(*[ba_covariance_pair(*map(int, p)) for p in pairs])
+        out = np.zeros(n * COV_SLOT)
+        found = np.zeros(n, np.int32)
+        rc = self._L.ba_covariance_blocks(self._handle(), n, C.cast(req, C.c_void_p), out.ctypes.data, found.ctypes.data)
+        if rc != COV_OK:
+            raise RuntimeError(self._L.ba_last_error().decode())
+        res = []
+        for k, (ka, ia, kb, ib) in enumerate(pairs):
+            if not found[k]:
+                res.append(None)
+                continue
+            da, db = self.block_dim(ka, ia), self.block_dim(kb, ib)
+            res.append(out[k * COV_SLOT: k * COV_SLOT + da * db].reshape(da, db).copy())
+        return res
+
+    def block(self, kind_a: int, index_a: int, kind_b: Optional[int] = None, index_b: Optional[int] = None):
+        if kind_b is None:
+            kind_b, index_b = kind_a, index_a
+        return self.blocks([(kind_a, index_a, kind_b, index_b)])[0]
+
+    def timing(self) -> dict:
+        v = [C.c_double(0.0) for _ in range(4)]
+        n, n_inv = C.c_int32(0), C.c_int32(0)
+        self._L.ba_covariance_timing(self._handle(), *[C.byref(x) for x in v], C.byref(n), C.byref(n_inv))
+        return {"form_ms": v[0].value, "factor_ms": v[1].value, "inverse_ms": v[2].value, "extract_ms": v[3].value,
+                "n": int(n.value), "n_inverted": int(n_inv.value)}
+
+
+last_covariance_message = ""  # ba_last_error() of the last estimate that was not estimable
+
+
+def estimate_covariance_flat(fp: FlatProblem, options: Optional[BACovarianceOptions] = None,
+                             so: Optional[SolverOptions] = None, gpu_index: int = -1) -> Optional[FlatCovariance]:
+    """ba_estimate_covariance on a flat problem at its current parameter values (the arrays are only read).
+    None: not estimable (the message is in `last_covariance_message`); RuntimeError on errors."""
+    global last_covariance_message
+    options = options or BACovarianceOptions()
+    so = so or SolverOptions()
+    p = marshal_problem(fp)
+    o = marshal_options(so)
+    co = ba_covariance_options(int(options.params), float(options.damping))
+    L = lib()
+    _check_abi(L)
+    _cov_prototypes(L)
+    h = C.c_void_p()
+    rc = L.ba_estimate_covariance(C.addressof(p), C.addressof(o), C.addressof(co), gpu_index, C.byref(h))
+    if rc == COV_NOT_ESTIMABLE:
+        last_covariance_message = L.ba_last_error().decode()
+        import logging
+        logging.getLogger(__name__).warning(last_covariance_message)
+        return None
+    if rc != COV_OK:
+        raise RuntimeError(L.ba_last_error().decode())
+    return FlatCovariance(L, h, len(fp.points))
+
+
+class BACovariance:
+    """colmap::BACovariance: queries by image / point id and by parameter array, over a FlatCovariance."""
+
+    def __init__(self, flat: FlatCovariance, pose_of_image: Dict[int, int], point_index: Dict[int, int],
+                 others: List[tuple]):
+        self.flat_ = flat
+        self._pose_of_image = pose_of_image
+        self._point_index = point_index
+        self._others = others  # (parameter array, kind, index)
+
+    def GetPointCov(self, point3D_id: int) -> Optional[np.ndarray]:
+        j = self._point_index.get(point3D_id)
+        return None if j is None else self.flat_.point(j)
+
+    def GetCamCovFromWorld(self, image_id: int) -> Optional[np.ndarray]:
+        i = self._pose_of_image.get(image_id)
+        return None if i is None else self.flat_.block(COV_KIND_POSE, i)
+
+    def GetCamCrossCovFromWorld(self, image_id1: int, image_id2: int) -> Optional[np.ndarray]:
+        i1, i2 = self._pose_of_image.get(image_id1), self._pose_of_image.get(image_id2)
+        if i1 is None or i2 is None:
+            return None
+        return self.flat_.block(COV_KIND_POSE, i1, COV_KIND_POSE, i2)
+
+    def GetCam2CovFromCam1(self, image_id1: int, cam1_from_world: np.ndarray, image_id2: int,
+                           cam2_from_world: np.ndarray) -> Optional[np.ndarray]:
+        i1, i2 = self._pose_of_image.get(image_id1), self._pose_of_image.get(image_id2)
+        if i1 is None or i2 is None:
+            return None
+        c11, c22, c12 = self.flat_.blocks([(COV_KIND_POSE, i1, COV_KIND_POSE, i1), (COV_KIND_POSE, i2, COV_KIND_POSE, i2),
+                                           (COV_KIND_POSE, i1, COV_KIND_POSE, i2)])
+        if c11 is None or c22 is None or c11.shape[0] != 6 or c22.shape[0] != 6:
+            return None  # a pose that is (partially) constant
+        cov = np.zeros((12, 12))
+        cov[:6, :6], cov[6:, 6:], cov[:6, 6:], cov[6:, :6] = c11, c22, c12, c12.T
+        return scene.GetCovarianceForRelativeRigid3d(np.asarray(cam1_from_world), np.asarray(cam2_from_world), cov)
+
+    def GetOtherParamsCov(self, params) -> Optional[np.ndarray]:
+        for arr, kind, idx in self._others:
+            if arr is params:
+                return self.flat_.block(kind, idx)
+        return None
+
+
+def EstimateBACovariance(options: BACovarianceOptions, reconstruction: scene.Reconstruction,
+                         bundle_adjuster: BundleAdjuster, gpu_index: Optional[int] = None) -> Optional[BACovariance]:
+    """colmap::EstimateBACovariance for this backend: the problem the adjuster built (blocks, manifolds, loss, priors)
+    at its current values -- after Solve(), the solution. None when not estimable."""
+    for image_id in reconstruction.images:
+        if not reconstruction.IsRefInFrame(image_id):
+            raise ValueError(f"image {image_id} is not the reference sensor of its frame: covariances of non-trivial "
+                             "frames are not supported")
+    fp = bundle_adjuster.problem_
+    if gpu_index is None:
+        gpu = [int(x) for x in str(bundle_adjuster.options_.gpu_index).split(",") if x.strip()]
+        gpu_index = gpu[0] if gpu else -1
+    so = bundle_adjuster.options_.solver_options
+    flat = estimate_covariance_flat(fp, options, so, gpu_index)
+    if flat is None:
+        return None
+    pose_of_image = {}
+    for image_id, (pose_slot, _sens) in (fp.image_slots or {}).items():
+        if not fp.pose_const[pose_slot]:
+            pose_of_image[image_id] = pose_slot
+    point_index = {pid: j for j, pid in enumerate(fp.point_ids)}
+    others = [(reconstruction.cameras[cid].params, COV_KIND_CAMERA, k) for k, cid in enumerate(fp.cam_ids)]
+    if fp.sensors is not None and fp.sensor_ids:
+        for k, cid in enumerate(fp.sensor_ids):
+            for rig in reconstruction.rigs.values():
+                if cid in rig.sensors:
+                    others.append((rig.sensors[cid], COV_KIND_SENSOR, k))
+    return BACovariance(flat, pose_of_image, point_index, others)

@@ -44,3 +44,10 @@ def bundle_adjustment(reconstruction, options=None):
     ctl = bundle_adjuster.BundleAdjustmentController(options or estimators.BundleAdjustmentOptions(), reconstruction)
     ctl.Run()
     return ctl.summary
+
+
+def estimate_ba_covariance(options, reconstruction, bundle_adjuster):
+    """pycolmap.estimate_ba_covariance (pycolmap/estimators/covariance.cc): covariances of a solved bundle adjustment
+    on the GPU; None when they are not estimable."""
+    from . import estimators
+    return estimators.EstimateBACovariance(options, reconstruction, bundle_adjuster)

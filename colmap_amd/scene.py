@@ -595,3 +595,45 @@ def synthesize_flat(num_frames: int, num_points: int, track_length: int, seed: i
     return dict(poses=poses, cams=cams, cam_model=model, points=pts,
                 obs_pose=obs_pose.astype(np.int32), obs_cam=obs_pose.astype(np.int32),
                 obs_point=obs_point.astype(np.int32), obs_xy=xy)
+
+
+# ---------------------------------------------------------------------------------------------
+# Uncertainty propagation of Rigid3d (geometry/rigid3.h: Adjoint, AdjointInverse,
+# GetCovarianceForRelativeRigid3d). Poses are Rigid3d params (qx qy qz qw tx ty tz); tangent order
+# [rotation, translation].
+# ---------------------------------------------------------------------------------------------
+
+def cross_product_matrix(v: np.ndarray) -> np.ndarray:
+    return np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+
+
+def rigid3d_adjoint(params: np.ndarray) -> np.ndarray:
+    """Rigid3d::Adjoint: [[R, 0], [t x R, R]]."""
+    R = quat_to_rot(np.asarray(params[:4], np.float64))
+    A = np.zeros((6, 6))
+    A[:3, :3] = R
+    A[3:, :3] = cross_product_matrix(np.asarray(params[4:7], np.float64)) @ R
+    A[3:, 3:] = R
+    return A
+
+
+def rigid3d_adjoint_inverse(params: np.ndarray) -> np.ndarray:
+    """Rigid3d::AdjointInverse: [[R^T, 0], [-R^T [t]x, R^T]] (the inverse of the adjoint)."""
+    Rt = quat_to_rot(np.asarray(params[:4], np.float64)).T
+    A = np.zeros((6, 6))
+    A[:3, :3] = Rt
+    A[3:, :3] = -Rt @ cross_product_matrix(np.asarray(params[4:7], np.float64))
+    A[3:, 3:] = Rt
+    return A
+
+
+def GetCovarianceForRelativeRigid3d(a_from_c: np.ndarray, b_from_c: np.ndarray, covar: np.ndarray) -> np.ndarray:
+    """6 x 6 covariance of b_from_a from the 12 x 12 joint covariance of (a_from_c, b_from_c):
+    J covar J^T with J = [-Adj(b_from_c) Adj(a_from_c)^-1, I]."""
+    covar = np.asarray(covar, np.float64)
+    if covar.shape != (12, 12):
+        raise ValueError("covar must be 12 x 12")
+    J = np.zeros((6, 12))
+    J[:, :6] = -rigid3d_adjoint(b_from_c) @ rigid3d_adjoint_inverse(a_from_c)
+    J[:, 6:] = np.eye(6)
+    return J @ covar @ J.T

@@ -571,6 +571,34 @@ class Mi355xBundleAdjuster : public BundleAdjuster {
   size_t NumPoseBlocks() const { return pose_const_.size(); }
   size_t NumConstantPoseBlocks() const { return std::count(pose_const_.begin(), pose_const_.end(), 1); }
 
+  // What the covariance estimate (colmap_amd/ba_covariance.hpp) needs of the flattened problem: the ba_options a
+  // solve passes (loss, Jacobi scaling), the device, and the slots of the blocks (-1: not in the problem).
+  ba_options SolveOptions() const {
+    ba_options so = options_.mi355x->solver_options;
+    so.loss_type = static_cast<int32_t>(options_.mi355x->loss_function_type);
+    so.loss_scale = options_.mi355x->loss_function_scale;
+    return so;
+  }
+  int GpuIndex() const { return options_.gpu_index.empty() ? -1 : std::stoi(options_.gpu_index); }
+  // the variable pose block of an image that is the reference sensor of its frame (rig_from_world / cam_from_world)
+  int VariablePoseSlotOfImage(const Image& image) const {
+    const bool in_frame = image.frame_id.has_value();
+    const auto it = pose_index_.find(std::make_tuple(in_frame, in_frame ? *image.frame_id : image.image_id, false));
+    return it == pose_index_.end() ? -1 : it->second;
+  }
+  int PointSlotOf(point3D_t id) const {
+    const auto it = point_index_.find(id);
+    return it == point_index_.end() ? -1 : it->second;
+  }
+  int CamSlotOf(camera_t id) const {
+    const auto it = cam_index_.find(id);
+    return it == cam_index_.end() ? -1 : it->second;
+  }
+  int SensorSlotOf(camera_t id) const {
+    const auto it = sensor_index_.find(id);
+    return it == sensor_index_.end() ? -1 : it->second;
+  }
+
  private:
   struct PoseRef {
     bool is_frame;  // the block lives in a Frame (rig_from_world) or in an Image (cam_from_world)
