@@ -74,8 +74,8 @@ constexpr int PD = 6;        // pose tangent width (5 when the gauge holds a tra
 // The intrinsics tangent width KD (row stride of Jcam / cam_var) and the widest camera-side block BD
 // (stride of the per-chunk partials) are chosen per problem: <KD, BD> = <4, 6> when no camera has
 // more than 4 variable intrinsics (every model with the principal point fixed except OPENCV), else
-// <8, 8>. The kernels whose register footprint depends on them are templates; the others read
-// V.kd / V.bd.
+// <8, 8>, or <16, 16> (below). The kernels whose register footprint depends on them are templates
+// (instantiated through Solver::with_tier); the others read V.kd / V.bd.
 constexpr int KD_MAX = 8;
 constexpr int KD_WIDE = 16;  // FULL_OPENCV / THIN_PRISM_FISHEYE (12), RAD_TAN_THIN_PRISM_FISHEYE (16): third <KD, BD> tier
 constexpr int NPAR_WIDE = 16;
@@ -1553,38 +1553,8 @@ __global__ void ba_obs_jx_kernel(View V, const double* __restrict__ x, double* _
   pair_store(jx, o, a0, a1);  // c-order, coalesced
 }
 
-// model cost change: -(J step) . (r + J step / 2), step = (dc, dp) already negated
-__global__ void __launch_bounds__(256) ba_model_kernel(View V, const double* __restrict__ dc,
-                                                      const double* __restrict__ dp,
-                                                      double* __restrict__ partials) {
-  const int o = blockIdx.x * blockDim.x + threadIdx.x;
-  double acc = 0.0;
-  if (o < V.n_obs) {
-    const size_t N = (size_t)V.n_obs;
-    const int pi = V.o_pose[o], ci = V.o_cam[o], xi = V.o_pt[o];
-    const int pdim = V.pose_dim[pi], poff = V.pose_off[pi], cdim = V.cam_dim[ci], coff = V.cam_off[ci];
-    const int ptoff = V.pt_off[xi];
-    for (int r = 0; r < 2; ++r) {
-      double m = 0.0;
-      for (int c = 0; c < pdim; ++c) m += V.Jpose[(size_t)(r * PD + c) * N + o] * dc[poff + c];
-      for (int c = 0; c < cdim; ++c) m += V.Jcam[(size_t)(r * V.kd + c) * N + o] * dc[coff + c];
-      if (V.sens_off) {
-        const int si = V.o_sensor[o];
-        const int soff = si >= 0 ? V.sens_off[si] : -1;
-        if (soff >= 0)
-          for (int c = 0; c < 6; ++c) m += V.Jsens[(size_t)(r * 6 + c) * N + o] * dc[soff + c];
-      }
-      if (ptoff >= 0)
-        for (int c = 0; c < 3; ++c) m += V.Jpt[(size_t)(r * 3 + c) * N + V.c2a[o]] * dp[ptoff + c];
-      acc -= m * (V.res[r * N + o] + 0.5 * m);
-    }
-  }
-  acc = block_sum(acc);
-  if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-}
-
-// The same quantity from what the back-substitution left behind: jx = J_c y_c (p-order) is still in
-// place, so J step = -(jx + J_p y_p) needs only the point columns, the residual and jx (10 doubles per
+// Model cost change -(J step) . (r + J step / 2) from what the back-substitution left behind: jx = J_c y_c (p-order)
+// is still in place, so J step = -(jx + J_p y_p) needs only the point columns, the residual and jx (10 doubles per
 // observation instead of 28). Lane per point over its contiguous p-order segment; y_p = dpv (not negated).
 __global__ void __launch_bounds__(256) ba_model_from_jx_kernel(View V, const double* __restrict__ jx,
                                                               const double* __restrict__ dpv,
@@ -1798,8 +1768,8 @@ __global__ void ba_block_mat_finalize_kernel(View V, double* __restrict__ M) {
 // computed where C^-1 is local (ba_obs_schur_g_kernel, p-order) and stored in c-order. Observation
 // pairs of one point inside one block (shared intrinsics, rig frames) add their cross terms in
 // ba_block_schur_cross_kernel; the self term is already in (I - G).
-// One wave per chunk. Lane l holds column i = l & 15 and slab row k = l >> 4 (k = 2 * observation
-// in slab + residual row). C/D layout: col = l & 15, row = (l >> 4) + 4 * reg.
+// Lane l of a wave holds column i = l & 15 and slab row k = l >> 4 (k = 2 * observation in slab +
+// residual row). C/D layout: col = l & 15, row = (l >> 4) + 4 * reg.
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 // G_o = E_o C_j^-1 E_o^T (g00, g01, g11), lane per observation in p-order, stored at the c-order
@@ -1832,49 +1802,10 @@ __global__ void __launch_bounds__(256) ba_obs_schur_g_kernel(View V, const doubl
   rec[1] = make_double2(g11, 0.0);
 }
 
-__global__ void __launch_bounds__(64) ba_block_gram_kernel(View V, const double* __restrict__ G) {
-  const int ch = blockIdx.x;
-  const int b = V.chunk_blk[ch];
-  const int kind = V.blk_kind[b], dim = V.blk_dim[b];
-  const int lane = threadIdx.x;
-  const int i = lane & 15, k = lane >> 4;  // column, row-in-slab
-  const int r = k & 1, oo = k >> 1;        // residual row, observation within the slab
-  const int beg = V.chunk_beg[ch], end = V.chunk_end[ch];
-  v4f64 acc = {0.0, 0.0, 0.0, 0.0};
-  const bool col_ok = i < dim;
-  const double* col0 = col_ok ? blk_col(V, kind, 0, i) : nullptr;
-  const double* col1 = col_ok ? blk_col(V, kind, 1, i) : nullptr;
-  constexpr int U = 4;  // slabs per trip: the loads of four MFMAs are in flight together
-  for (int s = beg; s < end; s += 2 * U) {
-    double a[U], bb[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int idx = s + 2 * u + oo;
-      a[u] = bb[u] = 0.0;
-      if (col_ok && idx < end) {
-        const double j0 = col0[idx], j1 = col1[idx];
-        const double2 ga = reinterpret_cast<const double2*>(G)[2 * (size_t)idx];
-        const double g00 = ga.x, g01 = ga.y, g11 = G[4 * (size_t)idx + 2];
-        a[u] = r ? j1 : j0;
-        bb[u] = r ? j1 - (g01 * j0 + g11 * j1) : j0 - (g00 * j0 + g01 * j1);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], bb[u], acc, 0, 0, 0);
-  }
-#pragma unroll
-  for (int reg = 0; reg < 4; ++reg) {
-    const int row = k + 4 * reg;
-    if (row < dim && i < dim) V.cpart[(size_t)ch * V.bd * V.bd + row * dim + i] = acc[reg];
-  }
-}
-
-// The same contraction with the operands staged through LDS: per trip the wave loads 32 consecutive
-// observations of every Jacobian column of the block (and of G) as contiguous 256-byte segments -- half a
-// wave per (row, column) pair -- and the 16 slabs of the trip feed the matrix core from LDS. In the kernel
-// above every lane loads its own operand: 16 different columns per load instruction. Same slabs, same zero
-// padding; the trips of a chunk are dealt to four waves whose tiles are added at the end, so the result differs
-// from the kernel above by the order of the additions (rounding).
+// The contraction with its operands staged through LDS: per trip a wave loads 32 consecutive observations of every
+// Jacobian column of the block (and of G) as contiguous 256-byte segments -- half a wave per (row, column) pair --
+// and the 16 slabs of the trip feed the matrix core from LDS (operands loaded lane by lane would touch 16 different
+// columns per load instruction).
 constexpr int GRAM_TRIP = 32;
 constexpr int GRAM_WAVES = 4;
 template <int BD>  // widest block of the problem: bounds the prefetch registers (6, 8 or 16 column pairs per lane)
@@ -2357,82 +2288,6 @@ __global__ void ba_pcg_dir_kernel(int n, const double* __restrict__ scalars, con
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   p[i] = first ? z[i] : z[i] + (pcg_rho(part, nparts) / scalars[S_RHO_LAST]) * p[i];
-}
-// One single-workgroup kernel per PCG iteration for everything around the three streaming kernels of the
-// implicit product (single GPU, no priors; the sharded / prior path keeps the separate kernels because
-// all-reduces sit between the steps). A lane owns whole blocks, so every step below touches only entries
-// the same lane produced -- the only synchronisations are the three workgroup sums:
-//   tail of iteration k : q_b = Dc_b^2 p_b + sum of the block's J_b^T v chunk partials; pq = p.q;
-//                         alpha = rho / pq; x += alpha p; r -= alpha q; Q = -x.(b + r) / 2
-//   head of iteration k+1: z_b = Minv_b r_b; rho' = r.z; p = z + (rho' / rho) p
-// HEAD_ONLY starts a solve: x = 0, r = b, p = z = Minv b. scalars: S_RHO = the rho iteration k used (what
-// the host tests), S_RHO_LAST = rho' for the next call, S_PQ, S_Q.
-template <bool HEAD_ONLY>
-__global__ void __launch_bounds__(1024) ba_pcg_fused_kernel(View V, const double* __restrict__ Dc,
-                                                            const double* __restrict__ Minv,
-                                                            const double* __restrict__ rhs, double* __restrict__ scalars,
-                                                            double* __restrict__ x, double* __restrict__ r,
-                                                            double* __restrict__ z, double* __restrict__ p,
-                                                            double* __restrict__ q) {
-  const int bd2 = V.bd * V.bd;
-  double rho = HEAD_ONLY ? 0.0 : scalars[S_RHO_LAST];
-  if (!HEAD_ONLY) {
-    double pq = 0.0;
-    for (int b = threadIdx.x; b < V.n_blk; b += 1024) {
-      const int dim = V.blk_dim[b], off = V.blk_off[b];
-      for (int c = 0; c < dim; ++c) {
-        double sacc = 0.0;
-        for (int ch = V.blk_chunk_ptr[b]; ch < V.blk_fin_end[b]; ++ch) sacc += V.cpart[(size_t)ch * bd2 + c];
-        const double d = Dc[off + c], pv = p[off + c];
-        const double qv = d * d * pv + sacc;
-        q[off + c] = qv;
-        pq += pv * qv;
-      }
-    }
-    pq = block_sum(pq);
-    const double alpha = rho / pq;
-    double Q = 0.0;
-    for (int b = threadIdx.x; b < V.n_blk; b += 1024) {
-      const int dim = V.blk_dim[b], off = V.blk_off[b];
-      for (int c = 0; c < dim; ++c) {
-        const double xn = x[off + c] + alpha * p[off + c];
-        const double rn = r[off + c] - alpha * q[off + c];
-        x[off + c] = xn;
-        r[off + c] = rn;
-        Q += -0.5 * xn * (rhs[off + c] + rn);
-      }
-    }
-    Q = block_sum(Q);
-    if (threadIdx.x == 0) {
-      scalars[S_Q] = Q;
-      scalars[S_PQ] = pq;
-      scalars[S_RHO] = rho;
-    }
-  }
-  double rho_new = 0.0;
-  for (int b = threadIdx.x; b < V.n_blk; b += 1024) {
-    const int n = V.blk_dim[b], off = V.blk_off[b];
-    const double* Mi = Minv + V.blk_moff[b];
-    for (int i = 0; i < n; ++i) {
-      if (HEAD_ONLY) { x[off + i] = 0.0; r[off + i] = rhs[off + i]; }
-    }
-    for (int i = 0; i < n; ++i) {
-      double sacc = 0.0;
-      for (int j = 0; j < n; ++j) sacc += Mi[i * n + j] * r[off + j];
-      z[off + i] = sacc;
-      rho_new += sacc * r[off + i];
-    }
-  }
-  rho_new = block_sum(rho_new);
-  const double beta = HEAD_ONLY ? 0.0 : rho_new / rho;
-  for (int b = threadIdx.x; b < V.n_blk; b += 1024) {
-    const int n = V.blk_dim[b], off = V.blk_off[b];
-    for (int i = 0; i < n; ++i) p[off + i] = HEAD_ONLY ? z[off + i] : z[off + i] + beta * p[off + i];
-  }
-  if (threadIdx.x == 0) {
-    scalars[S_RHO_LAST] = rho_new;
-    if (HEAD_ONLY) scalars[S_RHO] = rho_new;
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -3200,6 +3055,14 @@ static inline bool ba_debug() { return dev_switch_int("COLMAP_AMD_BA_DEBUG", 0) 
     }                                                                                  \
   } while (0)
 
+// The three width tiers <KD, BD> of a problem (see the constants at the top of the file), as types whose widths
+// instantiate the kernels. KDT: the width of the pair / incidence kernels (KD_MAX serves both narrow tiers).
+template <int KD_, int BD_, int KDT_>
+struct Tier {
+  static constexpr int kd = KD_, bd = BD_, kdt = KDT_;
+};
+enum TierId { TIER_NARROW, TIER_MAX, TIER_WIDE };
+
 struct Solver {
   const ba_options& opt;
   ba_problem& prob;
@@ -3257,7 +3120,8 @@ struct Solver {
   long long n_paired_kind[3] = {0, 0, 0};
   Buf<int> a_boff[3];
   Buf<double> Wp[3];
-  int kd = 4, bd = PD;  // intrinsics tangent width / widest camera-side block of this problem
+  int width_tier = TIER_NARROW;  // <KD, BD> of this problem, chosen in build()
+  int kd = 4, bd = PD;           // its intrinsics tangent width / widest camera-side block
   std::vector<int> h_pose_off, h_cam_off, h_pt_off;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
   hipStream_t st_chol = nullptr;  // second stream + events of the Cholesky lookahead (exact tiers)
@@ -3281,6 +3145,17 @@ struct Solver {
     if (st_chol) (void)hipStreamDestroy(st_chol);
     ba_explicit::free_pair_lists(pair_lists);
     if (st) (void)hipStreamDestroy(st);
+  }
+
+  // f(Tier<...>{}) for the width tier of this problem: the one place that maps it to template instantiations
+  template <typename F>
+  void with_tier(F&& f) const {
+    switch (width_tier) {
+      case TIER_NARROW: f(Tier<4, PD, KD_MAX>{}); return;
+      case TIER_MAX: f(Tier<KD_MAX, KD_MAX, KD_MAX>{}); return;
+      case TIER_WIDE: f(Tier<KD_WIDE, KD_WIDE, KD_WIDE>{}); return;
+    }
+    throw std::runtime_error("unknown width tier " + std::to_string(width_tier));
   }
 
   // Before a finalize kernel: the heavy blocks' rows summed into their first row (ba_cpart_heavy_reduce_kernel).
@@ -3352,9 +3227,8 @@ struct Solver {
     }
     // <KD, BD> of this problem (see the constants at the top of the file); a 12-parameter model takes
     // the wide tier whatever its number of variable intrinsics (only that tier evaluates 12 J_params columns)
-    if (max_npar > NPAR || max_nvar > KD_MAX) kd = bd = KD_WIDE;
-    else if (max_nvar <= 4) { kd = 4; bd = PD; }
-    else kd = bd = KD_MAX;
+    width_tier = max_npar > NPAR || max_nvar > KD_MAX ? TIER_WIDE : (max_nvar <= 4 ? TIER_NARROW : TIER_MAX);
+    with_tier([&](auto t) { kd = t.kd; bd = t.bd; });
     std::vector<int> h_cam_var((size_t)p.num_cams * kd, 0);
     for (int k = 0; k < p.num_cams; ++k)
       for (int d = 0; d < cam_nvar[k]; ++d) h_cam_var[(size_t)k * kd + d] = wide_cam_var[(size_t)k * KD_WIDE + d];
@@ -3839,8 +3713,7 @@ struct Solver {
     jx.alloc(2 * N); v.alloc(2 * N); Gobs.alloc(4 * N);
     if (n_var_sensors > 0) Jsens.alloc(12 * N);
     {
-      const bool op32_env = dev_switch_int("COLMAP_AMD_BA_OPERATOR_F32", 0) != 0;
-      op32 = (op32_env || opt.operator_precision == BA_OPERATOR_F32) && n_var_sensors == 0 && V.n_tiles > 0 && comm.world == 1;
+      op32 = opt.operator_precision == BA_OPERATOR_F32 && n_var_sensors == 0 && V.n_tiles > 0 && comm.world == 1;
       if (op32) { Jpose32.alloc(2 * PD * N); Jcam32.alloc(2 * (size_t)kd * N); Jpt32.alloc(6 * N); }
       V.Jpose32 = op32 ? Jpose32.p : nullptr;
       V.Jcam32 = op32 ? Jcam32.p : nullptr;
@@ -3909,7 +3782,7 @@ struct Solver {
 
   void launch_linearize(bool jac, const double* P, const double* Cm, const double* X, const double* Sn, int slot) {
     const int g = grid_for(V.n_obs, 256);
-    if (split_linearize && kd == 4 && plain_model >= 0) {
+    if (split_linearize && width_tier == TIER_NARROW && plain_model >= 0) {
       // one camera model, no rig observations, trivial loss, no fp32 copies: the PLAIN instantiations (same bits)
       auto launch = [&](auto tag) {
         constexpr int M = decltype(tag)::value;
@@ -3925,26 +3798,17 @@ struct Solver {
       if (plain_model == BA_SIMPLE_PINHOLE) launch(std::integral_constant<int, BA_SIMPLE_PINHOLE>{});
       else if (plain_model == BA_PINHOLE) launch(std::integral_constant<int, BA_PINHOLE>{});
       else launch(std::integral_constant<int, BA_SIMPLE_RADIAL>{});
-    } else if (jac && split_linearize) {  // camera side in c-order, point side in p-order: every store coalesced
-      if (kd == 4) {
-        BA_LAUNCH((ba_linearize_kernel<true, 4, false>), dim3(g), dim3(256), st, V, P, Cm, X, Sn, partials.p);
-        BA_LAUNCH((ba_linearize_point_kernel<4>), dim3(g), dim3(256), st, V, P, Cm, X, Sn);
-      } else if (kd == KD_WIDE) {
-        BA_LAUNCH((ba_linearize_kernel<true, KD_WIDE, false>), dim3(g), dim3(256), st, V, P, Cm, X, Sn, partials.p);
-        BA_LAUNCH((ba_linearize_point_kernel<KD_WIDE>), dim3(g), dim3(256), st, V, P, Cm, X, Sn);
-      } else {
-        BA_LAUNCH((ba_linearize_kernel<true, KD_MAX, false>), dim3(g), dim3(256), st, V, P, Cm, X, Sn, partials.p);
-        BA_LAUNCH((ba_linearize_point_kernel<KD_MAX>), dim3(g), dim3(256), st, V, P, Cm, X, Sn);
-      }
-    } else if (kd == 4) {
-      if (jac) BA_LAUNCH((ba_linearize_kernel<true, 4>), dim3(g), dim3(256), st, V, P, Cm, X, Sn, partials.p);
-      else BA_LAUNCH((ba_linearize_kernel<false, 4>), dim3(g), dim3(256), st, V, P, Cm, X, Sn, partials.p);
-    } else if (kd == KD_WIDE) {
-      if (jac) BA_LAUNCH((ba_linearize_kernel<true, KD_WIDE>), dim3(g), dim3(256), st, V, P, Cm, X, Sn, partials.p);
-      else BA_LAUNCH((ba_linearize_kernel<false, KD_WIDE>), dim3(g), dim3(256), st, V, P, Cm, X, Sn, partials.p);
     } else {
-      if (jac) BA_LAUNCH((ba_linearize_kernel<true, KD_MAX>), dim3(g), dim3(256), st, V, P, Cm, X, Sn, partials.p);
-      else BA_LAUNCH((ba_linearize_kernel<false, KD_MAX>), dim3(g), dim3(256), st, V, P, Cm, X, Sn, partials.p);
+      with_tier([&](auto t) {
+        if (jac && split_linearize) {  // camera side in c-order, point side in p-order: every store coalesced
+          BA_LAUNCH((ba_linearize_kernel<true, t.kd, false>), dim3(g), dim3(256), st, V, P, Cm, X, Sn, partials.p);
+          BA_LAUNCH((ba_linearize_point_kernel<t.kd>), dim3(g), dim3(256), st, V, P, Cm, X, Sn);
+        } else if (jac) {
+          BA_LAUNCH((ba_linearize_kernel<true, t.kd>), dim3(g), dim3(256), st, V, P, Cm, X, Sn, partials.p);
+        } else {
+          BA_LAUNCH((ba_linearize_kernel<false, t.kd>), dim3(g), dim3(256), st, V, P, Cm, X, Sn, partials.p);
+        }
+      });
     }
     BA_LAUNCH(ba_final_sum_kernel, dim3(1), dim3(1024), st, partials.p, g, scalars.p + slot);
     if (use_priors()) {
@@ -3959,9 +3823,9 @@ struct Solver {
       BA_HIP(hipMemsetAsync(gc.p, 0, sizeof(double) * std::max(V.n_c, 1), st));
       BA_HIP(hipMemsetAsync(diag_c.p, 0, sizeof(double) * std::max(V.n_c, 1), st));
     } else {
-      if (bd == PD) BA_LAUNCH((ba_block_jtv_kernel<true, PD>), dim3(V.n_chunks), dim3(64), st, V, res.p, gc.p, diag_c.p);
-      else if (bd == KD_WIDE) BA_LAUNCH((ba_block_jtv_kernel<true, KD_WIDE>), dim3(V.n_chunks), dim3(64), st, V, res.p, gc.p, diag_c.p);
-      else BA_LAUNCH((ba_block_jtv_kernel<true, KD_MAX>), dim3(V.n_chunks), dim3(64), st, V, res.p, gc.p, diag_c.p);
+      with_tier([&](auto t) {
+        BA_LAUNCH((ba_block_jtv_kernel<true, t.bd>), dim3(V.n_chunks), dim3(64), st, V, res.p, gc.p, diag_c.p);
+      });
       heavy_reduce(2 * bd);
       BA_LAUNCH(ba_block_vec_finalize_kernel<true>, dim3(grid_for(V.n_blk * bd, 128)), dim3(128), st, V, gc.p, diag_c.p);
     }
@@ -3984,9 +3848,7 @@ struct Solver {
   void block_jtv_reduced(const double* vin, const double* x_for_priors = nullptr) {
     if (V.n_chunks == 0) BA_HIP(hipMemsetAsync(tmpc.p, 0, sizeof(double) * std::max(V.n_c, 1), st));
     if (V.n_chunks > 0) {
-      if (bd == PD) BA_LAUNCH((ba_block_jtv_kernel<false, PD>), dim3(V.n_chunks), dim3(64), st, V, vin, tmpc.p, nullptr);
-      else if (bd == KD_WIDE) BA_LAUNCH((ba_block_jtv_kernel<false, KD_WIDE>), dim3(V.n_chunks), dim3(64), st, V, vin, tmpc.p, nullptr);
-      else BA_LAUNCH((ba_block_jtv_kernel<false, KD_MAX>), dim3(V.n_chunks), dim3(64), st, V, vin, tmpc.p, nullptr);
+      chunk_jtv(vin);
       heavy_reduce(bd);
       BA_LAUNCH(ba_block_vec_finalize_kernel<false>, dim3(grid_for(V.n_blk * bd, 128)), dim3(128), st, V, tmpc.p, nullptr);
     }
@@ -4017,12 +3879,7 @@ struct Solver {
       BA_LAUNCH(ba_block_vec_finalize_q_kernel, dim3(grid_for(V.n_blk * bd, 128)), dim3(128), st, V, Dc.p, xin, qout);
       return;
     }
-    const int go = grid_for(V.n_obs, 256);
-    if (V.n_obs > 0) {
-      if (kd == 4) BA_LAUNCH(ba_obs_jx_kernel<4>, dim3(go), dim3(256), st, V, xin, jx.p);
-      else if (kd == KD_WIDE) BA_LAUNCH(ba_obs_jx_kernel<KD_WIDE>, dim3(go), dim3(256), st, V, xin, jx.p);
-      else BA_LAUNCH(ba_obs_jx_kernel<KD_MAX>, dim3(go), dim3(256), st, V, xin, jx.p);
-    }
+    if (V.n_obs > 0) obs_jx(xin);
     if (comm.world == 1 || comm.by_point) {
       point_pass<0>();  // E^T x, C^-1 and E u of a point are local
     } else {
@@ -4082,52 +3939,34 @@ struct Solver {
     return 1;
   }
 
-  // The three streaming kernels of one implicit product on a single GPU: J_c p (c-order -> p-order),
-  // the point pass, J_c^T v into per-chunk partials. ba_pcg_fused_kernel finishes the product.
-  void schur_streams(const double* xin, bool use32) {
-    const int go = grid_for(V.n_obs, 256);
-    if (use32) {  // the inexact inner solve streams the fp32 copies of the columns (fp64 accumulation)
-      if (kd == 4) BA_LAUNCH((ba_obs_jx_kernel<4, float>), dim3(go), dim3(256), st, V, xin, jx.p);
-      else if (kd == KD_WIDE) BA_LAUNCH((ba_obs_jx_kernel<KD_WIDE, float>), dim3(go), dim3(256), st, V, xin, jx.p);
-      else BA_LAUNCH((ba_obs_jx_kernel<KD_MAX, float>), dim3(go), dim3(256), st, V, xin, jx.p);
-      BA_LAUNCH((ba_point_pass_tiled_kernel<0, float>), dim3(V.n_tiles), dim3(TILE_PTS), st, V, Cinv.p, jx.p, gp.p, v.p, dp.p);
-      if (bd == PD) BA_LAUNCH((ba_block_jtv_kernel<false, PD, float>), dim3(V.n_chunks), dim3(64), st, V, v.p, tmpc.p, nullptr);
-      else if (bd == KD_WIDE) BA_LAUNCH((ba_block_jtv_kernel<false, KD_WIDE, float>), dim3(V.n_chunks), dim3(64), st, V, v.p, tmpc.p, nullptr);
-      else BA_LAUNCH((ba_block_jtv_kernel<false, KD_MAX, float>), dim3(V.n_chunks), dim3(64), st, V, v.p, tmpc.p, nullptr);
-      return;
-    }
-    if (kd == 4) BA_LAUNCH(ba_obs_jx_kernel<4>, dim3(go), dim3(256), st, V, xin, jx.p);
-    else if (kd == KD_WIDE) BA_LAUNCH(ba_obs_jx_kernel<KD_WIDE>, dim3(go), dim3(256), st, V, xin, jx.p);
-    else BA_LAUNCH(ba_obs_jx_kernel<KD_MAX>, dim3(go), dim3(256), st, V, xin, jx.p);
-    point_pass<0>();
-    if (bd == PD) BA_LAUNCH((ba_block_jtv_kernel<false, PD>), dim3(V.n_chunks), dim3(64), st, V, v.p, tmpc.p, nullptr);
-    else if (bd == KD_WIDE) BA_LAUNCH((ba_block_jtv_kernel<false, KD_WIDE>), dim3(V.n_chunks), dim3(64), st, V, v.p, tmpc.p, nullptr);
-    else BA_LAUNCH((ba_block_jtv_kernel<false, KD_MAX>), dim3(V.n_chunks), dim3(64), st, V, v.p, tmpc.p, nullptr);
+  // jx = J_c x (c-order pairs), one lane per observation
+  template <typename JT = double>
+  void obs_jx(const double* xin) {
+    with_tier([&](auto t) {
+      BA_LAUNCH((ba_obs_jx_kernel<t.kd, JT>), dim3(grid_for(V.n_obs, 256)), dim3(256), st, V, xin, jx.p);
+    });
   }
 
-  int pcg_fused(int max_iter, double q_tol) {
-    BA_LAUNCH(ba_pcg_fused_kernel<true>, dim3(1), dim3(1024), st, V, Dc.p, Minv.p, rhs.p, scalars.p, x.p, r.p, z.p, pdir.p, q.p);
-    if (scalar(S_RHO) == 0.0) return 0;
-    double Q0 = 0.0;
-    int it;
-    for (it = 1; it <= max_iter; ++it) {
-      BA_HIP(hipEventRecord(ev0, st));
-      schur_streams(pdir.p, op32);
-      BA_HIP(hipEventRecord(ev1, st));
-      heavy_reduce(bd);
-      BA_LAUNCH(ba_pcg_fused_kernel<false>, dim3(1), dim3(1024), st, V, Dc.p, Minv.p, rhs.p, scalars.p, x.p, r.p, z.p, pdir.p, q.p);
-      double h[NSCALAR];
-      BA_HIP(hipMemcpyAsync(h, scalars.p, sizeof(h), hipMemcpyDeviceToHost, st));
-      BA_HIP(hipStreamSynchronize(st));
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) { g_spmv_ms += ms; g_spmv_launches += 1; }
-      const double rho = h[S_RHO], pq = h[S_PQ], Q1 = h[S_Q];
-      if (!(rho > 0.0) || !std::isfinite(rho) || !(pq > 0.0) || !std::isfinite(pq)) break;
-      const double zeta = it * (Q1 - Q0) / Q1;
-      if (zeta < q_tol) break;
-      Q0 = Q1;
+  // J_c^T v of every chunk into its partials (the block sums are left to a finalize kernel), v in c-order pairs
+  template <typename JT = double>
+  void chunk_jtv(const double* vin) {
+    with_tier([&](auto t) {
+      BA_LAUNCH((ba_block_jtv_kernel<false, t.bd, JT>), dim3(V.n_chunks), dim3(64), st, V, vin, tmpc.p, nullptr);
+    });
+  }
+
+  // The three streaming kernels of one implicit product on a single GPU: J_c p (c-order -> p-order),
+  // the point pass, J_c^T v into per-chunk partials. The caller finishes the product from the partials.
+  void schur_streams(const double* xin, bool use32) {
+    if (use32) {  // the inexact inner solve streams the fp32 copies of the columns (fp64 accumulation)
+      obs_jx<float>(xin);
+      BA_LAUNCH((ba_point_pass_tiled_kernel<0, float>), dim3(V.n_tiles), dim3(TILE_PTS), st, V, Cinv.p, jx.p, gp.p, v.p, dp.p);
+      chunk_jtv<float>(v.p);
+      return;
     }
-    return std::min(it, max_iter);
+    obs_jx(xin);
+    point_pass<0>();
+    chunk_jtv(v.p);
   }
 
   int pcg_pipelined(int max_iter, double q_tol) {
@@ -4146,9 +3985,9 @@ struct Solver {
     }
     PcgDev D;
     D.part = pcgp_part.p; D.nparts = nparts; D.stop = pcgp_stop.p; D.host = pcgp_host_dev; D.qhist = pcgp_qhist.p;
-    if (bd == PD) BA_LAUNCH(ba_pcgp_init_kernel<PD>, dim3(nparts), dim3(PCGP_T), st, V, D, Minv.p, rhs.p, x.p, r.p, z.p);
-    else if (bd == KD_MAX) BA_LAUNCH(ba_pcgp_init_kernel<KD_MAX>, dim3(nparts), dim3(PCGP_T), st, V, D, Minv.p, rhs.p, x.p, r.p, z.p);
-    else BA_LAUNCH(ba_pcgp_init_kernel<KD_WIDE>, dim3(nparts), dim3(PCGP_T), st, V, D, Minv.p, rhs.p, x.p, r.p, z.p);
+    with_tier([&](auto t) {
+      BA_LAUNCH(ba_pcgp_init_kernel<t.bd>, dim3(nparts), dim3(PCGP_T), st, V, D, Minv.p, rhs.p, x.p, r.p, z.p);
+    });
     V.stop = pcgp_stop.p;  // the streaming kernels of an iteration enqueued past convergence return at entry
     auto enqueue = [&](int k) {
       BA_LAUNCH(ba_pcgp_dir_kernel, dim3(gv), dim3(256), st, n, D, k, max_iter, q_tol, z.p, pdir.p);
@@ -4168,16 +4007,10 @@ struct Solver {
         comm.allreduce(tmpc.p, (size_t)n, st);
         reduced = tmpc.p;
       }
-      if (bd == PD) {
-        BA_LAUNCH(ba_pcgp_tail_kernel<PD>, dim3(nparts), dim3(PCGP_T), st, V, D, k, Dc.p, pdir.p, q.p, reduced);
-        BA_LAUNCH(ba_pcgp_step_kernel<PD>, dim3(nparts), dim3(PCGP_T), st, V, D, k, Minv.p, rhs.p, pdir.p, q.p, x.p, r.p, z.p);
-      } else if (bd == KD_MAX) {
-        BA_LAUNCH(ba_pcgp_tail_kernel<KD_MAX>, dim3(nparts), dim3(PCGP_T), st, V, D, k, Dc.p, pdir.p, q.p, reduced);
-        BA_LAUNCH(ba_pcgp_step_kernel<KD_MAX>, dim3(nparts), dim3(PCGP_T), st, V, D, k, Minv.p, rhs.p, pdir.p, q.p, x.p, r.p, z.p);
-      } else {
-        BA_LAUNCH(ba_pcgp_tail_kernel<KD_WIDE>, dim3(nparts), dim3(PCGP_T), st, V, D, k, Dc.p, pdir.p, q.p, reduced);
-        BA_LAUNCH(ba_pcgp_step_kernel<KD_WIDE>, dim3(nparts), dim3(PCGP_T), st, V, D, k, Minv.p, rhs.p, pdir.p, q.p, x.p, r.p, z.p);
-      }
+      with_tier([&](auto t) {
+        BA_LAUNCH(ba_pcgp_tail_kernel<t.bd>, dim3(nparts), dim3(PCGP_T), st, V, D, k, Dc.p, pdir.p, q.p, reduced);
+        BA_LAUNCH(ba_pcgp_step_kernel<t.bd>, dim3(nparts), dim3(PCGP_T), st, V, D, k, Minv.p, rhs.p, pdir.p, q.p, x.p, r.p, z.p);
+      });
     };
     enqueue(1);
     BA_HIP(hipEventSynchronize(pcgp_ev_dir[1]));
@@ -4198,18 +4031,12 @@ struct Solver {
   }
 
   int pcg(int max_iter, double q_tol) {
-    // measured at BA-1: the single-workgroup kernel takes 133 us against 54 us for the five small kernels it
-    // replaces (a lane's blocks are chains of dependent global loads that one workgroup cannot hide): opt-in only
-    const bool fused_env = dev_switch_int("COLMAP_AMD_BA_PCG_FUSED", 0) != 0;
-    if (fused_env && comm.world == 1 && !use_priors() && V.n_chunks > 0 && V.n_obs > 0 && V.n_blk <= 65536)
-      return pcg_fused(max_iter, q_tol);
     // single GPU, no priors: three small kernels per iteration, stopping test on the device, host one iteration
-    // behind (COLMAP_AMD_BA_PCG_PIPELINED=0: the step-by-step loop below, which sharded / prior solves always take)
-    const bool pipelined = dev_switch_int("COLMAP_AMD_BA_PCG_PIPELINED", 1) != 0;
-    // ... and point-sharded solves whose ranks all hold observations (pcg_all_ranks_have_work: agreed once per solve,
-    // the ranks must take the same path); image-sharded ones all-reduce inside the point pass as well and keep the loop below
+    // behind -- and point-sharded solves whose ranks all hold observations (pcg_all_ranks_have_work: agreed once per
+    // solve, the ranks must take the same path). Prior solves and image-sharded ones (which all-reduce inside the
+    // point pass as well) take the step-by-step loop below.
     const bool local_ok = !use_priors() && V.n_chunks > 0 && V.n_obs > 0;
-    if (pipelined && local_ok && (comm.world == 1 || (comm.by_point && pcg_all_ranks_have_work))) {
+    if (local_ok && (comm.world == 1 || (comm.by_point && pcg_all_ranks_have_work))) {
       ++g_pcg_pipelined_solves;
       return pcg_pipelined(max_iter, q_tol);
     }
@@ -4418,59 +4245,44 @@ struct Solver {
           else
             BA_LAUNCH(ba_obs_schur_g_kernel, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V, Cinv.p, Gobs.p);
           BA_HIP(hipEventRecord(ev2, st));
-          const bool gram_lds = dev_switch_int("COLMAP_AMD_BA_GRAM_LDS", 1) != 0;
-          if (gram_lds && bd == PD) BA_LAUNCH(ba_block_gram_lds_kernel<PD>, dim3(V.n_chunks), dim3(64 * GRAM_WAVES), st, V, Gobs.p);
-          else if (gram_lds && bd == KD_MAX) BA_LAUNCH(ba_block_gram_lds_kernel<KD_MAX>, dim3(V.n_chunks), dim3(64 * GRAM_WAVES), st, V, Gobs.p);
-          else if (gram_lds) BA_LAUNCH(ba_block_gram_lds_kernel<KD_WIDE>, dim3(V.n_chunks), dim3(64 * GRAM_WAVES), st, V, Gobs.p);
-          else BA_LAUNCH(ba_block_gram_kernel, dim3(V.n_chunks), dim3(64), st, V, Gobs.p);
+          with_tier([&](auto t) {
+            BA_LAUNCH(ba_block_gram_lds_kernel<t.bd>, dim3(V.n_chunks), dim3(64 * GRAM_WAVES), st, V, Gobs.p);
+          });
           BA_HIP(hipEventRecord(ev3, st));
           mfma_pending = true;
           heavy_reduce(bd * bd);
           BA_LAUNCH(ba_block_mat_finalize_kernel<false>, dim3(grid_for(V.n_blk * bd * bd, 128)), dim3(128), st, V, M.p);
           if (n_paired > 0) {  // observation pairs of a point inside one block: shared intrinsics, rig frames
-            if (bd == PD) BA_LAUNCH(ba_obs_w_kernel<PD>, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V);
-            else if (bd == KD_WIDE) BA_LAUNCH(ba_obs_w_kernel<KD_WIDE>, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V);
-            else BA_LAUNCH(ba_obs_w_kernel<KD_MAX>, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V);
-            if (PV.n > 0) {  // per incidence (single GPU)
-              if (bd == KD_WIDE) {
-                BA_LAUNCH(ba_pair_cross_kernel<KD_WIDE>, dim3(PV.n_chunks), dim3(KD_WIDE * KD_WIDE), st, V, PV, Cinv.p);
-                BA_LAUNCH(ba_pair_finalize_kernel<KD_WIDE>, dim3(n_pair_blk, KD_WIDE * KD_WIDE / 64), dim3(1024), st, V, PV, pv_pair_blk.p, M.p);
-              } else {
-                BA_LAUNCH(ba_pair_cross_kernel<KD_MAX>, dim3(PV.n_chunks), dim3(KD_MAX * KD_MAX), st, V, PV, Cinv.p);
-                BA_LAUNCH(ba_pair_finalize_kernel<KD_MAX>, dim3(n_pair_blk, 1), dim3(1024), st, V, PV, pv_pair_blk.p, M.p);
+            with_tier([&](auto t) {
+              BA_LAUNCH(ba_obs_w_kernel<t.bd>, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V);
+              if (PV.n > 0) {  // per incidence (single GPU)
+                BA_LAUNCH(ba_pair_cross_kernel<t.kdt>, dim3(PV.n_chunks), dim3(t.kdt * t.kdt), st, V, PV, Cinv.p);
+                BA_LAUNCH(ba_pair_finalize_kernel<t.kdt>, dim3(n_pair_blk, t.kdt * t.kdt / 64), dim3(1024), st, V, PV, pv_pair_blk.p, M.p);
+              } else {  // per observation (sharded solves: the local pairs)
+                BA_LAUNCH(ba_block_schur_cross_kernel<t.bd>, dim3(V.n_chunks), dim3(64), st, V, Cinv.p);
+                heavy_reduce(bd * bd);
+                BA_LAUNCH(ba_block_mat_finalize_kernel<true>, dim3(grid_for(V.n_blk * bd * bd, 128)), dim3(128), st, V, M.p);
               }
-            } else {  // per observation (sharded solves: the local pairs)
-              if (bd == PD) BA_LAUNCH(ba_block_schur_cross_kernel<PD>, dim3(V.n_chunks), dim3(64), st, V, Cinv.p);
-              else if (bd == KD_WIDE) BA_LAUNCH(ba_block_schur_cross_kernel<KD_WIDE>, dim3(V.n_chunks), dim3(64), st, V, Cinv.p);
-              else BA_LAUNCH(ba_block_schur_cross_kernel<KD_MAX>, dim3(V.n_chunks), dim3(64), st, V, Cinv.p);
-              heavy_reduce(bd * bd);
-              BA_LAUNCH(ba_block_mat_finalize_kernel<true>, dim3(grid_for(V.n_blk * bd * bd, 128)), dim3(128), st, V, M.p);
-            }
+            });
           }
         }
         if (use_priors())
           BA_LAUNCH(ba_prior_accumulate_kernel<1>, dim3(grid_for(Q.n_tblk, 64)), dim3(64), st, V, Q, M.p, nullptr);
         if (IV.n > 0) {  // image sharding: pairs of observations of a point in a shared intrinsics block on different ranks
-          const int gi = grid_for(IV.n, 128);
-          const size_t wn = (size_t)IV.n * (kd == KD_WIDE ? KD_WIDE : KD_MAX) * 3;
-          if (kd == KD_WIDE) BA_LAUNCH(ba_inc_w_kernel<KD_WIDE>, dim3(gi), dim3(128), st, V, IV, inc_wloc.p);
-          else BA_LAUNCH(ba_inc_w_kernel<KD_MAX>, dim3(gi), dim3(128), st, V, IV, inc_wloc.p);
-          BA_HIP(hipMemcpyAsync(inc_wtot.p, inc_wloc.p, sizeof(double) * wn, hipMemcpyDeviceToDevice, st));
-          comm.allreduce(inc_wtot.p, wn, st);
-          if (kd == KD_WIDE) {
-            BA_LAUNCH(ba_inc_correct_kernel<KD_WIDE>, dim3(IV.n_chunks), dim3(KD_WIDE * KD_WIDE), st, V, IV, Cinv.p, inc_wloc.p,
+          with_tier([&](auto t) {
+            const size_t wn = (size_t)IV.n * t.kdt * 3;
+            BA_LAUNCH(ba_inc_w_kernel<t.kdt>, dim3(grid_for(IV.n, 128)), dim3(128), st, V, IV, inc_wloc.p);
+            BA_HIP(hipMemcpyAsync(inc_wtot.p, inc_wloc.p, sizeof(double) * wn, hipMemcpyDeviceToDevice, st));
+            comm.allreduce(inc_wtot.p, wn, st);
+            BA_LAUNCH(ba_inc_correct_kernel<t.kdt>, dim3(IV.n_chunks), dim3(t.kdt * t.kdt), st, V, IV, Cinv.p, inc_wloc.p,
                       inc_wtot.p, comm.rank, comm.world);
-            BA_LAUNCH(ba_inc_finalize_kernel<KD_WIDE>, dim3(grid_for((size_t)V.n_blk * KD_WIDE * KD_WIDE, 256)), dim3(256), st, V, IV, M.p);
-          } else {
-            BA_LAUNCH(ba_inc_correct_kernel<KD_MAX>, dim3(IV.n_chunks), dim3(KD_MAX * KD_MAX), st, V, IV, Cinv.p, inc_wloc.p,
-                      inc_wtot.p, comm.rank, comm.world);
-            BA_LAUNCH(ba_inc_finalize_kernel<KD_MAX>, dim3(grid_for((size_t)V.n_blk * KD_MAX * KD_MAX, 256)), dim3(256), st, V, IV, M.p);
-          }
+            BA_LAUNCH(ba_inc_finalize_kernel<t.kdt>, dim3(grid_for((size_t)V.n_blk * t.kdt * t.kdt, 256)), dim3(256), st, V, IV, M.p);
+          });
         }
         comm.allreduce(M.p, (size_t)moff_total, st);
-        if (bd == PD) BA_LAUNCH(ba_block_invert_kernel<PD>, dim3(grid_for(V.n_blk, 64)), dim3(64), st, V, Dc.p, M.p, Minv.p);
-        else if (bd == KD_WIDE) BA_LAUNCH(ba_block_invert_kernel<KD_WIDE>, dim3(grid_for(V.n_blk, 64)), dim3(64), st, V, Dc.p, M.p, Minv.p);
-        else BA_LAUNCH(ba_block_invert_kernel<KD_MAX>, dim3(grid_for(V.n_blk, 64)), dim3(64), st, V, Dc.p, M.p, Minv.p);
+        with_tier([&](auto t) {
+          BA_LAUNCH(ba_block_invert_kernel<t.bd>, dim3(grid_for(V.n_blk, 64)), dim3(64), st, V, Dc.p, M.p, Minv.p);
+        });
         // reduced rhs = g_c - E C^-1 g_p  (g_p, C^-1 are global; the J_c^T part is summed over ranks)
         if (!rhs_pass_fused) point_pass<1>();
         block_jtv_reduced(v.p);
@@ -4480,11 +4292,7 @@ struct Solver {
         out->total_linear_iterations += lin_iters;
       }
       // back-substitution y_p = C^-1 (g_p - E^T y_c); step = -(y_c, y_p)
-      if (V.n_obs > 0) {
-        if (kd == 4) BA_LAUNCH(ba_obs_jx_kernel<4>, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V, x.p, jx.p);
-        else if (kd == KD_WIDE) BA_LAUNCH(ba_obs_jx_kernel<KD_WIDE>, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V, x.p, jx.p);
-        else BA_LAUNCH(ba_obs_jx_kernel<KD_MAX>, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V, x.p, jx.p);
-      }
+      if (V.n_obs > 0) obs_jx(x.p);
       // (tiles: the same launch leaves the model cost change's partial sums behind -- columns, jx and y_p are in its registers)
       const bool model_fused = (comm.world == 1 || comm.by_point) && V.n_tiles > 0;
       if (model_fused) {

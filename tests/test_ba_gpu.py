@@ -443,19 +443,6 @@ def test_plain_linearisation_is_bit_identical(model):
     assert np.array_equal(b0.poses, b1.poses) and np.array_equal(b0.points, b1.points) and np.array_equal(b0.cams, b1.cams)
 
 
-def test_fused_pcg_kernel_matches_separate_kernels():
-    """ba_pcg_fused_kernel (one single-workgroup kernel around the three streaming kernels of a product) against
-    the separate precondition / direction / finalize / update kernels: same algorithm, different summation
-    trees -- cost log to 1e-12, identical PCG iteration counts."""
-    fp = _flat(40, 3000, 8, seed=6)
-    assert est.fix_gauge_two_cams(fp)
-    b0, s0 = _solve_env(fp, {"COLMAP_AMD_BA_PCG_FUSED": "0"}, max_num_iterations=12)
-    b1, s1 = _solve_env(fp, {"COLMAP_AMD_BA_PCG_FUSED": "1"}, max_num_iterations=12)
-    np.testing.assert_allclose(s1.log_cost, s0.log_cost, rtol=1e-12)
-    np.testing.assert_array_equal(s1.log_linear_iters, s0.log_linear_iters)
-    np.testing.assert_allclose(b1.points, b0.points, atol=1e-10)
-
-
 @pytest.mark.parametrize("frames,points,track,mixed", [(40, 2000, 8, True), (200, 20000, 10, False)])
 def test_fp32_operator_reaches_the_fp64_solution(frames, points, track, mixed):
     """ba_options.operator_precision = BA_OPERATOR_F32: the inexact inner CG solve streams fp32 copies of the
