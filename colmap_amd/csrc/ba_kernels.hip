@@ -3023,6 +3023,31 @@ struct Buf {
   ~Buf() { release(); }
 };
 
+// Owning stream / event handles: created in place, destroyed with their owner, converted to the raw handle on use.
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  void create() { BA_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  void create_lowest_priority() {
+    int prio_least = 0, prio_greatest = 0;
+    BA_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    BA_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio_least));
+  }
+  ~Stream() { if (s) (void)hipStreamDestroy(s); }
+  operator hipStream_t() const { return s; }
+};
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  void create(bool timing = true) { BA_HIP(timing ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  operator hipEvent_t() const { return e; }
+};
+
 inline int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
 
 // Host-side set-up loops over the observations (gathers into the device orders: random reads that one core serves at
@@ -3062,13 +3087,15 @@ struct Tier {
   static constexpr int kd = KD_, bd = BD_, kdt = KDT_;
 };
 enum TierId { TIER_NARROW, TIER_MAX, TIER_WIDE };
+struct CovHandle;
 
 struct Solver {
   const ba_options& opt;
   ba_problem& prob;
   Comm& comm;
   View V{};
-  hipStream_t st = nullptr;
+  const std::chrono::steady_clock::time_point t_entry = std::chrono::steady_clock::now();  // setup_seconds counts from here
+  Stream st;
   // topology
   Buf<int> o_sensor, sens_off;
   Buf<double> sensors, sensors2, Jsens;
@@ -3103,7 +3130,7 @@ struct Solver {
   Buf<int> pcgp_stop;
   PcgHostSlot* pcgp_host = nullptr;      // [2], hipHostMalloc
   PcgHostSlot* pcgp_host_dev = nullptr;  // the same, as the device sees it
-  hipEvent_t pcgp_ev_dir[2] = {nullptr, nullptr}, pcgp_ev_s0[2] = {nullptr, nullptr}, pcgp_ev_s1[2] = {nullptr, nullptr};
+  Event pcgp_ev_dir[2], pcgp_ev_s0[2], pcgp_ev_s1[2];
   Buf<double> Sdense;  // exact tiers: the reduced camera system, n_c x n_c
   Buf<double> chol_linv, chol_tmp;  // blocked Cholesky workspace (ba_schur_explicit.h)
   Buf<int> chol_info;
@@ -3123,29 +3150,20 @@ struct Solver {
   int width_tier = TIER_NARROW;  // <KD, BD> of this problem, chosen in build()
   int kd = 4, bd = PD;           // its intrinsics tangent width / widest camera-side block
   std::vector<int> h_pose_off, h_cam_off, h_pt_off;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-  hipStream_t st_chol = nullptr;  // second stream + events of the Cholesky lookahead (exact tiers)
+  Event ev0, ev1, ev2, ev3;
+  Stream st_chol;  // second stream + events of the Cholesky lookahead (exact tiers)
   ba_explicit::PairLists pair_lists;  // pair-major formation of the exact tiers (built with the solve's other structures)
-  hipEvent_t ev_chol_panel = nullptr, ev_chol_u2 = nullptr;
+  Event ev_chol_panel, ev_chol_u2;
 
-  Solver(ba_problem& p_, const ba_options& o_, Comm& c_) : opt(o_), prob(p_), comm(c_) {}
-  ~Solver() {
-    for (int k = 0; k < 2; ++k) {
-      if (pcgp_ev_dir[k]) (void)hipEventDestroy(pcgp_ev_dir[k]);
-      if (pcgp_ev_s0[k]) (void)hipEventDestroy(pcgp_ev_s0[k]);
-      if (pcgp_ev_s1[k]) (void)hipEventDestroy(pcgp_ev_s1[k]);
-    }
-    if (pcgp_host) (void)hipHostFree(pcgp_host);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (ev2) (void)hipEventDestroy(ev2);
-    if (ev3) (void)hipEventDestroy(ev3);
-    if (ev_chol_panel) (void)hipEventDestroy(ev_chol_panel);
-    if (ev_chol_u2) (void)hipEventDestroy(ev_chol_u2);
-    if (st_chol) (void)hipStreamDestroy(st_chol);
-    ba_explicit::free_pair_lists(pair_lists);
-    if (st) (void)hipStreamDestroy(st);
+  Solver(ba_problem& p_, const ba_options& o_, Comm& c_) : opt(o_), prob(p_), comm(c_) {
+    st.create();
+    for (Event* e : {&ev0, &ev1, &ev2, &ev3}) e->create();
   }
+  ~Solver() {
+    if (pcgp_host) (void)hipHostFree(pcgp_host);
+    ba_explicit::free_pair_lists(pair_lists);
+  }
+  bool points_local() const { return comm.world == 1 || comm.by_point; }  // a point's observations are all on this rank
 
   // f(Tier<...>{}) for the width tier of this problem: the one place that maps it to template instantiations
   template <typename F>
@@ -3880,8 +3898,8 @@ struct Solver {
       return;
     }
     if (V.n_obs > 0) obs_jx(xin);
-    if (comm.world == 1 || comm.by_point) {
-      point_pass<0>();  // E^T x, C^-1 and E u of a point are local
+    if (points_local()) {
+      point_pass<0>();
     } else {
       BA_HIP(hipMemsetAsync(tbuf.p, 0, sizeof(double) * std::max(V.n_p, 1), st));
       BA_LAUNCH(ba_point_t_kernel, dim3(grid_for(V.n_points, 128)), dim3(128), st, V, jx.p, tbuf.p);
@@ -3906,8 +3924,42 @@ struct Solver {
     fa.sens_off = V.sens_off;
     fa.fixed_point = opt.jacobi_scaling != 0;  // columns of norm < 1: integer accumulation, bit-reproducible
     fa.bad = chol_info.p + 1;                  // raised by a term the fixed point cannot hold (NaN, out of bound)
-    fa.pairs = nullptr;
-    return fa;
+    return fa;  // (pairs: form_reduced_system)
+  }
+
+  // Exact tiers: the reduced system of n columns (+ the row of the right-hand side, ba_explicit::factor_solve) and the
+  // Cholesky workspace. (The memsets run on the NULL stream: the caller synchronises the device before the first use.)
+  void prepare_exact(int n) {
+    Sdense.alloc((size_t)n * n + n);
+    if (dense_by_products) return;
+    chol_linv.alloc(ba_explicit::Workspace{}.linv_doubles(n)); chol_tmp.alloc(n); chol_info.alloc(2);  // [pivot flag, formation flag]
+  }
+  // Cholesky lookahead (unless COLMAP_AMD_BA_CHOL_LOOKAHEAD=0): the second stream carries bulk trailing updates that run
+  // beside the serial chain of small kernels on the main stream: lowest priority, so that a freed workgroup slot goes to
+  // the chain first. (The covariance path opens it after its one formation: 5 us of 90 with the second queue open.)
+  void open_cholesky_lookahead() {
+    if (dev_switch_int("COLMAP_AMD_BA_CHOL_LOOKAHEAD", 1) == 0) return;
+    st_chol.create_lowest_priority(); ev_chol_panel.create(false); ev_chol_u2.create(false);
+  }
+  auto cholesky_workspace() const {  // (no lookahead: its stream and events are null, which is how factor_solve is told)
+    ba_explicit::Workspace ws;
+    ws.Linv = chol_linv.p; ws.tmp = chol_tmp.p; ws.info = chol_info.p;
+    ws.st2 = st_chol; ws.ev_panel = ev_chol_panel; ws.ev_u2 = ev_chol_u2;
+    return ws;
+  }
+  // Pair-major formation: its incidence lists depend on the topology in `fa` only -- built once, with the other
+  // per-solve structures, not inside the LM loop (COLMAP_AMD_BA_FORM_PAIRS=0: the point-major kernel)
+  void build_pair_lists(const ba_explicit::FormArgs& fa) {
+    if (dev_switch_int("COLMAP_AMD_BA_FORM_PAIRS", 1) != 0) (void)ba_explicit::build_pair_lists(fa, pair_lists, st);
+  }
+  // Sdense = this rank's reduced camera system in the layout of `fa` (pair-major when the lists were built, else one
+  // wave per point), with the priors' rows at the given tangent offsets
+  void form_reduced_system(ba_explicit::FormArgs fa, const int* prior_pose_off, const int* prior_sens_off) {
+    fa.pairs = pair_lists.inc ? &pair_lists : nullptr;
+    ba_explicit::form(fa, Sdense.p, st);
+    if (use_priors())
+      ba_explicit::add_prior_rows(Sdense.p, fa.n_c, Q.J, prior_pose_off, prior_sens_off, Q.pdim, Q.n, fa.fixed_point, fa.bad, st);
+    ba_explicit::finish(Sdense.p, fa.n_c, fa.fixed_point, fa.bad, st);
   }
 
   // DENSE_SCHUR: x = S^-1 rhs with S built from n_c operator products
@@ -3915,19 +3967,12 @@ struct Solver {
     const int n = V.n_c;
     if (Sdense.n < (size_t)n * n + n) throw std::runtime_error("dense Schur buffer");
     if (!dense_by_products) {
-      // explicit formation (pair-major, or one wave per point) + blocked Cholesky on the f64 matrix cores
-      ba_explicit::FormArgs fa = form_args();
-      fa.pairs = pair_lists.inc ? &pair_lists : nullptr;
-      ba_explicit::form(fa, Sdense.p, st);
-      if (use_priors()) ba_explicit::add_prior_rows(Sdense.p, n, Q.J, Q.po, Q.so, Q.pdim, Q.n, fa.fixed_point, fa.bad, st);
-      ba_explicit::finish(Sdense.p, n, fa.fixed_point, fa.bad, st);
+      // explicit formation + blocked Cholesky on the f64 matrix cores
+      form_reduced_system(form_args(), Q.po, Q.so);
       if (comm.world > 1) comm.allreduce(Sdense.p, (size_t)n * n, st);  // point sharding: partial sums per rank
       ba_explicit::add_lm_diagonal(Sdense.p, n, Dc.p, st);
-      ba_explicit::Workspace ws;
-      ws.Linv = chol_linv.p; ws.tmp = chol_tmp.p; ws.info = chol_info.p;
-      ws.st2 = st_chol; ws.ev_panel = ev_chol_panel; ws.ev_u2 = ev_chol_u2;
       double ms = 0.0;
-      ba_explicit::factor_solve(Sdense.p, n, rhs.p, x.p, ws, st, ev0, ev1, &ms);
+      ba_explicit::factor_solve(Sdense.p, n, rhs.p, x.p, cholesky_workspace(), st, ev0, ev1, &ms);
       factor_ms += ms;
       return 1;
     }
@@ -3977,11 +4022,8 @@ struct Solver {
       pcgp_part.alloc((size_t)2 * 3 * nparts);
       pcgp_qhist.alloc(2);
       pcgp_stop.alloc(1);
-      for (int k = 0; k < 2; ++k) {
-        BA_HIP(hipEventCreateWithFlags(&pcgp_ev_dir[k], hipEventDisableTiming));
-        BA_HIP(hipEventCreate(&pcgp_ev_s0[k]));
-        BA_HIP(hipEventCreate(&pcgp_ev_s1[k]));
-      }
+      for (Event& e : pcgp_ev_dir) e.create(false);
+      for (Event* e : {&pcgp_ev_s0[0], &pcgp_ev_s0[1], &pcgp_ev_s1[0], &pcgp_ev_s1[1]}) e->create();
     }
     PcgDev D;
     D.part = pcgp_part.p; D.nparts = nparts; D.stop = pcgp_stop.p; D.host = pcgp_host_dev; D.qhist = pcgp_qhist.p;
@@ -4036,7 +4078,7 @@ struct Solver {
     // solve, the ranks must take the same path). Prior solves and image-sharded ones (which all-reduce inside the
     // point pass as well) take the step-by-step loop below.
     const bool local_ok = !use_priors() && V.n_chunks > 0 && V.n_obs > 0;
-    if (local_ok && (comm.world == 1 || (comm.by_point && pcg_all_ranks_have_work))) {
+    if (local_ok && points_local() && (comm.world == 1 || pcg_all_ranks_have_work)) {
       ++g_pcg_pipelined_solves;
       return pcg_pipelined(max_iter, q_tol);
     }
@@ -4086,54 +4128,184 @@ struct Solver {
                 sensors.p, sensors2.p);
   }
 
-  void run(ba_result* out) {
-    const auto t_entry = std::chrono::steady_clock::now();
-    BA_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    BA_HIP(hipEventCreate(&ev0));
-    BA_HIP(hipEventCreate(&ev1));
-    BA_HIP(hipEventCreate(&ev2));
-    BA_HIP(hipEventCreate(&ev3));
-    out->termination_type = BA_FAILURE;
-    const int n = build(out);
-    if (n == 0) return;
-    const int nc = V.n_c, np = V.n_p;
-    const int gvc = grid_for(nc, 256), gvp = grid_for(np, 256);
-    if (opt.linear_solver_type < BA_SOLVER_ITERATIVE_SCHUR || opt.linear_solver_type > BA_SOLVER_SPARSE_SCHUR)
-      throw std::runtime_error("linear_solver_type");
-    {
-      // CreateSolverOptions' rule (bundle_adjustment_ceres.cc:203-213, CPU thresholds bundle_adjustment_ceres.h:
-      // 68-69) on the number of pose blocks; both exact tiers run the explicit reduced camera system
-      const int lst = opt.linear_solver_type;
-      int tier = lst;
-      if (lst == BA_SOLVER_AUTO)
-        tier = prob.num_poses <= 50 ? BA_SOLVER_DENSE_SCHUR : (prob.num_poses <= 1000 ? BA_SOLVER_SPARSE_SCHUR : BA_SOLVER_ITERATIVE_SCHUR);
-      const bool want_exact = tier == BA_SOLVER_DENSE_SCHUR || tier == BA_SOLVER_SPARSE_SCHUR;
-      // an image-sharded solve splits a point's observations over the ranks: only the operator-product formation
-      // (every product is all-reduced) is correct there, and only affordable for small systems
-      dense_by_products = want_exact && comm.world > 1 && !comm.by_point;
-      if (want_exact && dev_switch_int("COLMAP_AMD_BA_DENSE_BY_PRODUCTS", 0) != 0) dense_by_products = true;
-      use_dense = want_exact && nc > 0 && nc <= (dense_by_products ? 1024 : 32768);
-      out->linear_solver_used = use_dense ? tier : BA_SOLVER_ITERATIVE_SCHUR;
-    }
-    if (use_dense) {
-      Sdense.alloc((size_t)nc * nc + nc);  // + the row of the right-hand side (ba_explicit::factor_solve)
-      if (!dense_by_products) {
-        ba_explicit::Workspace ws;
-        chol_linv.alloc(ws.linv_doubles(nc)); chol_tmp.alloc(nc); chol_info.alloc(2);  // [pivot flag, formation flag]
-        if (dev_switch_int("COLMAP_AMD_BA_CHOL_LOOKAHEAD", 1) != 0) {
-          // the second stream carries bulk trailing updates that run beside the serial chain of small kernels on the
-          // main stream: lowest priority, so that a freed workgroup slot goes to the chain first
-          int prio_least = 0, prio_greatest = 0;
-          BA_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-          BA_HIP(hipStreamCreateWithPriority(&st_chol, hipStreamNonBlocking, prio_least));
-          BA_HIP(hipEventCreateWithFlags(&ev_chol_panel, hipEventDisableTiming));
-          BA_HIP(hipEventCreateWithFlags(&ev_chol_u2, hipEventDisableTiming));
-        }
-        // pair-major formation: its incidence lists depend on the topology only -- built here, with the other
-        // per-solve structures, not inside the LM loop (COLMAP_AMD_BA_FORM_PAIRS=0: the point-major kernel)
-        if (dev_switch_int("COLMAP_AMD_BA_FORM_PAIRS", 1) != 0) (void)ba_explicit::build_pair_lists(form_args(), pair_lists, st);
+  // Which tier solves the reduced system: CreateSolverOptions' rule (bundle_adjustment_ceres.cc:203-213, CPU thresholds
+  // bundle_adjustment_ceres.h:68-69) on the number of pose blocks; both exact tiers run the explicit reduced system
+  void choose_linear_solver(ba_result* out) {
+    const int lst = opt.linear_solver_type, nc = V.n_c;
+    if (lst < BA_SOLVER_ITERATIVE_SCHUR || lst > BA_SOLVER_SPARSE_SCHUR) throw std::runtime_error("linear_solver_type");
+    int tier = lst;
+    if (lst == BA_SOLVER_AUTO)
+      tier = prob.num_poses <= 50 ? BA_SOLVER_DENSE_SCHUR : (prob.num_poses <= 1000 ? BA_SOLVER_SPARSE_SCHUR : BA_SOLVER_ITERATIVE_SCHUR);
+    const bool want_exact = tier == BA_SOLVER_DENSE_SCHUR || tier == BA_SOLVER_SPARSE_SCHUR;
+    // an image-sharded solve splits a point's observations over the ranks: only the operator-product formation
+    // (every product is all-reduced) is correct there, and only affordable for small systems
+    dense_by_products = want_exact && !points_local();
+    if (want_exact && dev_switch_int("COLMAP_AMD_BA_DENSE_BY_PRODUCTS", 0) != 0) dense_by_products = true;
+    use_dense = want_exact && nc > 0 && nc <= (dense_by_products ? 1024 : 32768);
+    out->linear_solver_used = use_dense ? tier : BA_SOLVER_ITERATIVE_SCHUR;
+  }
+
+  // column scales of both sides from the squared column norms (jacobi = 0: unit scales)
+  void set_scales(int jacobi) {
+    BA_LAUNCH(ba_scale_kernel, dim3(std::max(grid_for(V.n_c, 256), 1)), dim3(256), st, V.n_c, diag_c.p, jacobi, scale_c.p);
+    BA_LAUNCH(ba_scale_kernel, dim3(std::max(grid_for(V.n_p, 256), 1)), dim3(256), st, V.n_p, diag_p.p, jacobi, scale_p.p);
+  }
+  // Jacobian, cost, gradient and squared column norms at the current parameters
+  void linearize() {
+    launch_linearize(true, poses.p, cams.p, points.p, sensors.p, S_COST);
+    gradient_and_diag();
+  }
+  // The first linearisation of a solve (after set_scales(0)): Jacobi scaling from the initial Jacobian, then
+  // re-linearised with it
+  void initial_linearization() {
+    linearize();
+    set_scales(opt.jacobi_scaling);
+    linearize();
+  }
+  // Dc, Dp = the LM diagonal at this trust-region radius; Cinv = the inverted damped point blocks
+  void damp(double radius) {
+    BA_LAUNCH(ba_lm_diag_kernel, dim3(std::max(grid_for(V.n_c, 256), 1)), dim3(256), st, V.n_c, diag_c.p, radius,
+              opt.min_lm_diagonal, opt.max_lm_diagonal, Dc.p);
+    BA_LAUNCH(ba_lm_diag_kernel, dim3(std::max(grid_for(V.n_p, 256), 1)), dim3(256), st, V.n_p, diag_p.p, radius,
+              opt.min_lm_diagonal, opt.max_lm_diagonal, Dp.p);
+    BA_LAUNCH(ba_point_blocks_kernel, dim3(grid_for(V.n_points, 128)), dim3(128), st, V, Craw.p, Dp.p, Cinv.p);
+  }
+
+  // tiles, points local: the reduced right-hand side's point pass -- which holds E_o and needs C^-1 anyway -- runs inside
+  // form_preconditioner() and leaves G_o behind (v is not touched until reduced_rhs())
+  bool rhs_pass_fused() const { return V.n_chunks > 0 && V.n_tiles > 0 && points_local(); }
+
+  // Minv = the inverted blocks of the Schur-Jacobi preconditioner. Returns whether its matrix-core kernel ran, between
+  // ev2 and ev3 (the caller adds their interval to g_mfma_ms after its next synchronisation)
+  bool form_preconditioner() {
+    if (V.n_chunks == 0) BA_HIP(hipMemsetAsync(M.p, 0, sizeof(double) * std::max(moff_total, 1), st));
+    if (V.n_chunks > 0) {  // (ba_block_mat_finalize_kernel<false> assigns every entry of every block)
+      if (rhs_pass_fused())
+        BA_LAUNCH((ba_point_pass_tiled_kernel<4>), dim3(V.n_tiles), dim3(TILE_PTS), st, V, Cinv.p, jx.p, gp.p, v.p, dp.p, (double*)nullptr, Gobs.p);
+      else
+        BA_LAUNCH(ba_obs_schur_g_kernel, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V, Cinv.p, Gobs.p);
+      BA_HIP(hipEventRecord(ev2, st));
+      with_tier([&](auto t) {
+        BA_LAUNCH(ba_block_gram_lds_kernel<t.bd>, dim3(V.n_chunks), dim3(64 * GRAM_WAVES), st, V, Gobs.p);
+      });
+      BA_HIP(hipEventRecord(ev3, st));
+      heavy_reduce(bd * bd);
+      BA_LAUNCH(ba_block_mat_finalize_kernel<false>, dim3(grid_for(V.n_blk * bd * bd, 128)), dim3(128), st, V, M.p);
+      if (n_paired > 0) {  // observation pairs of a point inside one block: shared intrinsics, rig frames
+        with_tier([&](auto t) {
+          BA_LAUNCH(ba_obs_w_kernel<t.bd>, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V);
+          if (PV.n > 0) {  // per incidence (single GPU)
+            BA_LAUNCH(ba_pair_cross_kernel<t.kdt>, dim3(PV.n_chunks), dim3(t.kdt * t.kdt), st, V, PV, Cinv.p);
+            BA_LAUNCH(ba_pair_finalize_kernel<t.kdt>, dim3(n_pair_blk, t.kdt * t.kdt / 64), dim3(1024), st, V, PV, pv_pair_blk.p, M.p);
+          } else {  // per observation (sharded solves: the local pairs)
+            BA_LAUNCH(ba_block_schur_cross_kernel<t.bd>, dim3(V.n_chunks), dim3(64), st, V, Cinv.p);
+            heavy_reduce(bd * bd);
+            BA_LAUNCH(ba_block_mat_finalize_kernel<true>, dim3(grid_for(V.n_blk * bd * bd, 128)), dim3(128), st, V, M.p);
+          }
+        });
       }
-      BA_HIP(hipDeviceSynchronize());  // the allocation's memset runs on the NULL stream
+    }
+    if (use_priors())
+      BA_LAUNCH(ba_prior_accumulate_kernel<1>, dim3(grid_for(Q.n_tblk, 64)), dim3(64), st, V, Q, M.p, nullptr);
+    if (IV.n > 0) {  // image sharding: pairs of observations of a point in a shared intrinsics block on different ranks
+      with_tier([&](auto t) {
+        const size_t wn = (size_t)IV.n * t.kdt * 3;
+        BA_LAUNCH(ba_inc_w_kernel<t.kdt>, dim3(grid_for(IV.n, 128)), dim3(128), st, V, IV, inc_wloc.p);
+        BA_HIP(hipMemcpyAsync(inc_wtot.p, inc_wloc.p, sizeof(double) * wn, hipMemcpyDeviceToDevice, st));
+        comm.allreduce(inc_wtot.p, wn, st);
+        BA_LAUNCH(ba_inc_correct_kernel<t.kdt>, dim3(IV.n_chunks), dim3(t.kdt * t.kdt), st, V, IV, Cinv.p, inc_wloc.p,
+                  inc_wtot.p, comm.rank, comm.world);
+        BA_LAUNCH(ba_inc_finalize_kernel<t.kdt>, dim3(grid_for((size_t)V.n_blk * t.kdt * t.kdt, 256)), dim3(256), st, V, IV, M.p);
+      });
+    }
+    comm.allreduce(M.p, (size_t)moff_total, st);
+    with_tier([&](auto t) {
+      BA_LAUNCH(ba_block_invert_kernel<t.bd>, dim3(grid_for(V.n_blk, 64)), dim3(64), st, V, Dc.p, M.p, Minv.p);
+    });
+    return V.n_chunks > 0;
+  }
+
+  // rhs = g_c - E C^-1 g_p  (g_p, C^-1 are global; the J_c^T part is summed over ranks)
+  void reduced_rhs() {
+    if (!rhs_pass_fused()) point_pass<1>();
+    block_jtv_reduced(v.p);
+    BA_HIP(hipMemcpyAsync(rhs.p, gc.p, sizeof(double) * V.n_c, hipMemcpyDeviceToDevice, st));
+    BA_LAUNCH(ba_add_kernel, dim3(grid_for(V.n_c, 256)), dim3(256), st, V.n_c, tmpc.p, rhs.p);
+  }
+
+  // Back-substitution y_p = C^-1 (g_p - E^T y_c), step = -(y_c, y_p), and the model cost change
+  // -(J step).(r + J step / 2) into scalars[S_MODEL]
+  void back_substitute_and_model_change() {
+    if (V.n_obs > 0) obs_jx(x.p);
+    // (tiles: the same launch leaves the model cost change's partial sums behind -- columns, jx and y_p are in its registers)
+    const bool model_fused = points_local() && V.n_tiles > 0;
+    if (model_fused) {
+      BA_LAUNCH((ba_point_pass_tiled_kernel<3>), dim3(V.n_tiles), dim3(TILE_PTS), st, V, Cinv.p, jx.p, gp.p, v.p, dp.p, partials.p);
+    } else if (points_local()) {
+      point_pass<2>();
+    } else {
+      BA_HIP(hipMemsetAsync(tbuf.p, 0, sizeof(double) * std::max(V.n_p, 1), st));
+      BA_LAUNCH(ba_point_t_kernel, dim3(grid_for(V.n_points, 128)), dim3(128), st, V, jx.p, tbuf.p);
+      comm.allreduce(tbuf.p, V.n_p, st);
+      BA_LAUNCH(ba_point_apply_kernel<2>, dim3(grid_for(V.n_points, 128)), dim3(128), st, V, Cinv.p, jx.p, gp.p,
+                tbuf.p, v.p, dp.p);
+    }
+    // (the negated, unscaled camera-side step: only the priors' model term reads it; Plus() forms its own)
+    if (use_priors())
+      BA_LAUNCH(ba_axpby_kernel, dim3(std::max(grid_for(V.n_c, 256), 1)), dim3(256), st, V.n_c, -1.0, x.p, nullptr, stepc.p);
+    // jx = J_c y_c of the back-substitution is still in place
+    if (V.n_tiles == 0)
+      BA_LAUNCH(ba_model_from_jx_kernel, dim3(grid_for(V.n_points, 256)), dim3(256), st, V, jx.p, dp.p, partials.p);
+    else if (!model_fused)
+      BA_LAUNCH(ba_point_reduce_tiled_kernel<1>, dim3(V.n_tiles), dim3(TILE_PTS), st, V, jx.p, dp.p, partials.p, nullptr, nullptr);
+    BA_LAUNCH(ba_final_sum_kernel, dim3(1), dim3(1024), st, partials.p, V.n_tiles > 0 ? V.n_tiles : grid_for(V.n_points, 256),
+              scalars.p + S_MODEL);
+    if (use_priors()) BA_LAUNCH(ba_prior_model_kernel, dim3(1), dim3(256), st, Q, stepc.p, scalars.p + S_MODEL);
+  }
+
+  // candidate = Plus(x, step), the Jacobi scaling of the step undone, and its cost into scalars[S_NEWCOST]
+  void evaluate_candidate() {
+    apply_step(x.p, scale_c.p, dp.p, scale_p.p, 3, false, poses2.p, cams2.p, points2.p);  // step = (-y) * column scale
+    launch_linearize(false, poses2.p, cams2.p, points2.p, sensors2.p, S_NEWCOST);
+  }
+
+  // The result into the caller's arrays: variable blocks only (constant blocks stay bit-identical)
+  void write_back() {
+    auto copy_variable = [](double* dst, const std::vector<double>& src, const std::vector<int>& off, int count, size_t stride) {
+      for (int i = 0; i < count; ++i)
+        if (off[i] >= 0) std::memcpy(dst + stride * i, src.data() + stride * i, stride * sizeof(double));
+    };
+    BA_LAUNCH(ba_renorm_quat_kernel, dim3(grid_for(V.n_poses, 128)), dim3(128), st, V, poses.p);
+    if (comm.world > 1 && comm.by_point) {
+      // every rank moved its own points only: zero the others' variable points and sum over ranks
+      BA_LAUNCH(ba_keep_own_points_kernel, dim3(grid_for(V.n_points, 128)), dim3(128), st, V, comm.rank, comm.world, points.p);
+      comm.allreduce(points.p, 3 * (size_t)V.n_points, st);
+    }
+    if (V.sens_off) {
+      BA_LAUNCH(ba_renorm_sensor_quat_kernel, dim3(grid_for(V.n_sensors, 128)), dim3(128), st, V, sensors.p);
+      std::vector<double> hs(sensors.n);
+      BA_HIP(hipMemcpyAsync(hs.data(), sensors.p, sizeof(double) * sensors.n, hipMemcpyDeviceToHost, st));
+      BA_HIP(hipStreamSynchronize(st));
+      copy_variable(prob.sensors, hs, h_sens_off, prob.num_sensors, 7);
+    }
+    std::vector<double> hp(poses.n), hc(cams.n), hx(points.n);
+    BA_HIP(hipMemcpyAsync(hp.data(), poses.p, sizeof(double) * poses.n, hipMemcpyDeviceToHost, st));
+    BA_HIP(hipMemcpyAsync(hc.data(), cams.p, sizeof(double) * cams.n, hipMemcpyDeviceToHost, st));
+    BA_HIP(hipMemcpyAsync(hx.data(), points.p, sizeof(double) * points.n, hipMemcpyDeviceToHost, st));
+    BA_HIP(hipStreamSynchronize(st));
+    copy_variable(prob.poses, hp, h_pose_off, prob.num_poses, 7);
+    copy_variable(prob.cams, hc, h_cam_off, prob.num_cams, BA_CAM_STRIDE);
+    copy_variable(prob.points, hx, h_pt_off, prob.num_points, 3);
+  }
+
+  void run(ba_result* out) {
+    out->termination_type = BA_FAILURE;
+    if (build(out) == 0) return;
+    choose_linear_solver(out);
+    if (use_dense) {
+      prepare_exact(V.n_c);
+      if (!dense_by_products) open_cholesky_lookahead(), build_pair_lists(form_args());
+      BA_HIP(hipDeviceSynchronize());  // the allocations' memsets run on the NULL stream
     }
     if (comm.world > 1) {
       // which PCG loop runs must not depend on the rank: one sum over ranks of "this rank could not take the pipelined one"
@@ -4152,11 +4324,11 @@ struct Solver {
 
     double radius = opt.initial_trust_region_radius, decrease_factor = 2.0;
     int invalid_steps = 0;
-    bool need_linearize = true, have_scale = false;
+    bool need_linearize = true;
     double cost = 0.0;
-    // scale = 1 until computed
-    BA_LAUNCH(ba_scale_kernel, dim3(std::max(gvc, 1)), dim3(256), st, nc, diag_c.p, 0, scale_c.p);
-    BA_LAUNCH(ba_scale_kernel, dim3(std::max(gvp, 1)), dim3(256), st, np, diag_p.p, 0, scale_p.p);
+    auto decrease_radius = [&] { radius /= decrease_factor; decrease_factor *= 2.0; };
+    auto terminate = [&](int type, int iterations) { out->termination_type = type; out->num_iterations = iterations; };
+    set_scales(0);  // scale = 1 until computed
     BA_HIP(hipStreamSynchronize(st));
     const auto t_start = std::chrono::steady_clock::now();
     out->setup_seconds = std::chrono::duration<double>(t_start - t_entry).count();
@@ -4165,39 +4337,21 @@ struct Solver {
     auto user_stop = [&](int iteration, double cost_now, double cost_change, bool step_ok, double rad, int lin) -> bool {
       if (!opt.iteration_callback) return false;
       ba_iteration_summary sm;
-      sm.iteration = iteration;
-      sm.step_is_successful = step_ok ? 1 : 0;
-      sm.linear_solver_iterations = lin;
-      sm.cost = cost_now;
-      sm.cost_change = cost_change;
-      sm.trust_region_radius = rad;
+      sm.iteration = iteration; sm.step_is_successful = step_ok ? 1 : 0; sm.linear_solver_iterations = lin;
+      sm.cost = cost_now; sm.cost_change = cost_change; sm.trust_region_radius = rad;
       sm.cumulative_time_in_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
       const int rc = opt.iteration_callback(opt.iteration_callback_user, &sm);
       if (rc == BA_CALLBACK_CONTINUE) return false;
-      out->termination_type = rc == BA_CALLBACK_TERMINATE ? BA_USER_SUCCESS : BA_USER_FAILURE;
-      out->num_iterations = iteration;
+      terminate(rc == BA_CALLBACK_TERMINATE ? BA_USER_SUCCESS : BA_USER_FAILURE, iteration);
       return true;
     };
 
     for (int iter = 0;; ++iter) {
       if (need_linearize) {
-        launch_linearize(true, poses.p, cams.p, points.p, sensors.p, S_COST);
-        gradient_and_diag();
-        if (!have_scale) {
-          // Jacobi scaling from the initial Jacobian, then re-linearise with it
-          BA_LAUNCH(ba_scale_kernel, dim3(std::max(gvc, 1)), dim3(256), st, nc, diag_c.p,
-                             opt.jacobi_scaling, scale_c.p);
-          BA_LAUNCH(ba_scale_kernel, dim3(std::max(gvp, 1)), dim3(256), st, np, diag_p.p,
-                             opt.jacobi_scaling, scale_p.p);
-          launch_linearize(true, poses.p, cams.p, points.p, sensors.p, S_COST);
-          gradient_and_diag();
-          have_scale = true;
-        }
+        if (iter == 0) initial_linearization();
+        else linearize();
         const bool one_sync = comm.world == 1;  // cost and gradient norm read together below
-        if (!one_sync) {
-          cost = scalar_sum(S_COST);
-          if (iter == 0) out->initial_cost = cost;
-        }
+        if (!one_sync) cost = scalar_sum(S_COST);
         // projected-gradient test: ||x - Plus(x, -g)||_inf with the unscaled gradient g = s * g_scaled
         // (the stored Jacobian is column-scaled: g_scaled = s * g, so g = g_scaled / s)
         // (one launch: the step -g / s is formed on the fly, Plus() of all blocks, the max of the differences)
@@ -4208,125 +4362,39 @@ struct Solver {
           double h[NSCALAR];
           scalars_to_host(h);
           cost = h[S_COST];
-          if (iter == 0) out->initial_cost = cost;
           gmax = h[S_GMAX];
         } else {
           gmax = scalar_max(S_GMAX);
         }
+        if (iter == 0) out->initial_cost = cost;
         if (gmax <= opt.gradient_tolerance) {
-          out->termination_type = BA_CONVERGENCE;
-          out->num_iterations = iter;
+          terminate(BA_CONVERGENCE, iter);
           break;
         }
         need_linearize = false;
         if (iter == 0 && user_stop(0, cost, 0.0, true, radius, 0)) break;
       }
       if (iter >= opt.max_num_iterations) {
-        out->termination_type = BA_NO_CONVERGENCE;
-        out->num_iterations = iter;
+        terminate(BA_NO_CONVERGENCE, iter);
         break;
       }
-      // LM diagonal, point blocks, Schur-Jacobi preconditioner
-      BA_LAUNCH(ba_lm_diag_kernel, dim3(std::max(gvc, 1)), dim3(256), st, nc, diag_c.p, radius,
-                         opt.min_lm_diagonal, opt.max_lm_diagonal, Dc.p);
-      BA_LAUNCH(ba_lm_diag_kernel, dim3(std::max(gvp, 1)), dim3(256), st, np, diag_p.p, radius,
-                         opt.min_lm_diagonal, opt.max_lm_diagonal, Dp.p);
-      BA_LAUNCH(ba_point_blocks_kernel, dim3(grid_for(V.n_points, 128)), dim3(128), st, V, Craw.p, Dp.p, Cinv.p);
+      // the damped system at this radius, its linear solve, the step and its predicted decrease
+      damp(radius);
       int lin_iters = 0;
       bool mfma_pending = false;
-      if (nc > 0) {
-        if (V.n_chunks == 0) BA_HIP(hipMemsetAsync(M.p, 0, sizeof(double) * std::max(moff_total, 1), st));
-        const bool rhs_pass_fused = V.n_chunks > 0 && V.n_tiles > 0 && (comm.world == 1 || comm.by_point);
-        if (V.n_chunks > 0) {  // (ba_block_mat_finalize_kernel<false> assigns every entry of every block)
-          // (tiles, points local: the reduced right-hand side's point pass -- which holds E_o and needs C^-1 anyway --
-          //  leaves G_o behind; v is not touched until block_jtv_reduced below)
-          if (rhs_pass_fused)
-            BA_LAUNCH((ba_point_pass_tiled_kernel<4>), dim3(V.n_tiles), dim3(TILE_PTS), st, V, Cinv.p, jx.p, gp.p, v.p, dp.p, (double*)nullptr, Gobs.p);
-          else
-            BA_LAUNCH(ba_obs_schur_g_kernel, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V, Cinv.p, Gobs.p);
-          BA_HIP(hipEventRecord(ev2, st));
-          with_tier([&](auto t) {
-            BA_LAUNCH(ba_block_gram_lds_kernel<t.bd>, dim3(V.n_chunks), dim3(64 * GRAM_WAVES), st, V, Gobs.p);
-          });
-          BA_HIP(hipEventRecord(ev3, st));
-          mfma_pending = true;
-          heavy_reduce(bd * bd);
-          BA_LAUNCH(ba_block_mat_finalize_kernel<false>, dim3(grid_for(V.n_blk * bd * bd, 128)), dim3(128), st, V, M.p);
-          if (n_paired > 0) {  // observation pairs of a point inside one block: shared intrinsics, rig frames
-            with_tier([&](auto t) {
-              BA_LAUNCH(ba_obs_w_kernel<t.bd>, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V);
-              if (PV.n > 0) {  // per incidence (single GPU)
-                BA_LAUNCH(ba_pair_cross_kernel<t.kdt>, dim3(PV.n_chunks), dim3(t.kdt * t.kdt), st, V, PV, Cinv.p);
-                BA_LAUNCH(ba_pair_finalize_kernel<t.kdt>, dim3(n_pair_blk, t.kdt * t.kdt / 64), dim3(1024), st, V, PV, pv_pair_blk.p, M.p);
-              } else {  // per observation (sharded solves: the local pairs)
-                BA_LAUNCH(ba_block_schur_cross_kernel<t.bd>, dim3(V.n_chunks), dim3(64), st, V, Cinv.p);
-                heavy_reduce(bd * bd);
-                BA_LAUNCH(ba_block_mat_finalize_kernel<true>, dim3(grid_for(V.n_blk * bd * bd, 128)), dim3(128), st, V, M.p);
-              }
-            });
-          }
-        }
-        if (use_priors())
-          BA_LAUNCH(ba_prior_accumulate_kernel<1>, dim3(grid_for(Q.n_tblk, 64)), dim3(64), st, V, Q, M.p, nullptr);
-        if (IV.n > 0) {  // image sharding: pairs of observations of a point in a shared intrinsics block on different ranks
-          with_tier([&](auto t) {
-            const size_t wn = (size_t)IV.n * t.kdt * 3;
-            BA_LAUNCH(ba_inc_w_kernel<t.kdt>, dim3(grid_for(IV.n, 128)), dim3(128), st, V, IV, inc_wloc.p);
-            BA_HIP(hipMemcpyAsync(inc_wtot.p, inc_wloc.p, sizeof(double) * wn, hipMemcpyDeviceToDevice, st));
-            comm.allreduce(inc_wtot.p, wn, st);
-            BA_LAUNCH(ba_inc_correct_kernel<t.kdt>, dim3(IV.n_chunks), dim3(t.kdt * t.kdt), st, V, IV, Cinv.p, inc_wloc.p,
-                      inc_wtot.p, comm.rank, comm.world);
-            BA_LAUNCH(ba_inc_finalize_kernel<t.kdt>, dim3(grid_for((size_t)V.n_blk * t.kdt * t.kdt, 256)), dim3(256), st, V, IV, M.p);
-          });
-        }
-        comm.allreduce(M.p, (size_t)moff_total, st);
-        with_tier([&](auto t) {
-          BA_LAUNCH(ba_block_invert_kernel<t.bd>, dim3(grid_for(V.n_blk, 64)), dim3(64), st, V, Dc.p, M.p, Minv.p);
-        });
-        // reduced rhs = g_c - E C^-1 g_p  (g_p, C^-1 are global; the J_c^T part is summed over ranks)
-        if (!rhs_pass_fused) point_pass<1>();
-        block_jtv_reduced(v.p);
-        BA_HIP(hipMemcpyAsync(rhs.p, gc.p, sizeof(double) * nc, hipMemcpyDeviceToDevice, st));
-        BA_LAUNCH(ba_add_kernel, dim3(grid_for(nc, 256)), dim3(256), st, nc, tmpc.p, rhs.p);
+      if (V.n_c > 0) {
+        mfma_pending = form_preconditioner();
+        reduced_rhs();
         lin_iters = use_dense ? dense_schur() : pcg(opt.max_linear_solver_iterations, opt.eta);
         out->total_linear_iterations += lin_iters;
       }
-      // back-substitution y_p = C^-1 (g_p - E^T y_c); step = -(y_c, y_p)
-      if (V.n_obs > 0) obs_jx(x.p);
-      // (tiles: the same launch leaves the model cost change's partial sums behind -- columns, jx and y_p are in its registers)
-      const bool model_fused = (comm.world == 1 || comm.by_point) && V.n_tiles > 0;
-      if (model_fused) {
-        BA_LAUNCH((ba_point_pass_tiled_kernel<3>), dim3(V.n_tiles), dim3(TILE_PTS), st, V, Cinv.p, jx.p, gp.p, v.p, dp.p, partials.p);
-      } else if (comm.world == 1 || comm.by_point) {
-        point_pass<2>();
-      } else {
-        BA_HIP(hipMemsetAsync(tbuf.p, 0, sizeof(double) * std::max(np, 1), st));
-        BA_LAUNCH(ba_point_t_kernel, dim3(grid_for(V.n_points, 128)), dim3(128), st, V, jx.p, tbuf.p);
-        comm.allreduce(tbuf.p, np, st);
-        BA_LAUNCH(ba_point_apply_kernel<2>, dim3(grid_for(V.n_points, 128)), dim3(128), st, V, Cinv.p, jx.p, gp.p,
-                  tbuf.p, v.p, dp.p);
-      }
-      // (the negated, unscaled camera-side step: only the priors' model term reads it; Plus() forms its own)
-      if (use_priors()) BA_LAUNCH(ba_axpby_kernel, dim3(std::max(gvc, 1)), dim3(256), st, nc, -1.0, x.p, nullptr, stepc.p);
-      // model cost change -(J step).(r + J step / 2): jx = J_c y_c of the back-substitution is still in place
-      if (model_fused) {
-        BA_LAUNCH(ba_final_sum_kernel, dim3(1), dim3(1024), st, partials.p, V.n_tiles, scalars.p + S_MODEL);
-      } else if (V.n_tiles > 0) {
-        BA_LAUNCH(ba_point_reduce_tiled_kernel<1>, dim3(V.n_tiles), dim3(TILE_PTS), st, V, jx.p, dp.p, partials.p, nullptr, nullptr);
-        BA_LAUNCH(ba_final_sum_kernel, dim3(1), dim3(1024), st, partials.p, V.n_tiles, scalars.p + S_MODEL);
-      } else {
-        BA_LAUNCH(ba_model_from_jx_kernel, dim3(grid_for(V.n_points, 256)), dim3(256), st, V, jx.p, dp.p, partials.p);
-        BA_LAUNCH(ba_final_sum_kernel, dim3(1), dim3(1024), st, partials.p, grid_for(V.n_points, 256), scalars.p + S_MODEL);
-      }
-      if (use_priors()) BA_LAUNCH(ba_prior_model_kernel, dim3(1), dim3(256), st, Q, stepc.p, scalars.p + S_MODEL);
+      back_substitute_and_model_change();
       // Single GPU: the candidate is evaluated before the model change is known (it is almost always valid; an
       // invalid step wastes one cost evaluation) and both numbers come back with one synchronisation.
       const bool speculate = comm.world == 1;
-      double spec_new_cost = 0.0;
-      double model_change;
+      double spec_new_cost = 0.0, model_change;
       if (speculate) {
-        apply_step(x.p, scale_c.p, dp.p, scale_p.p, 3, false, poses2.p, cams2.p, points2.p);  // step = (-y) * column scale
-        launch_linearize(false, poses2.p, cams2.p, points2.p, sensors2.p, S_NEWCOST);
+        evaluate_candidate();
         double h[NSCALAR];
         scalars_to_host(h);
         model_change = h[S_MODEL];
@@ -4342,28 +4410,21 @@ struct Solver {
       double new_cost = cost;
       if (!(model_change > 0.0) || !std::isfinite(model_change)) {
         if (++invalid_steps >= opt.max_num_consecutive_invalid_steps) {
-          out->termination_type = BA_FAILURE;
-          out->num_iterations = iter + 1;
+          terminate(BA_FAILURE, iter + 1);
           break;
         }
-        radius /= decrease_factor;
-        decrease_factor *= 2.0;
+        decrease_radius();
       } else {
         invalid_steps = 0;
-        // undo the Jacobi scaling of the step and evaluate the candidate
-        if (speculate) {
-          new_cost = spec_new_cost;
-        } else {
-          apply_step(x.p, scale_c.p, dp.p, scale_p.p, 3, false, poses2.p, cams2.p, points2.p);
-          launch_linearize(false, poses2.p, cams2.p, points2.p, sensors2.p, S_NEWCOST);
+        new_cost = spec_new_cost;
+        if (!speculate) {
+          evaluate_candidate();
           new_cost = scalar_sum(S_NEWCOST);
         }
         const double rho = (cost - new_cost) / model_change;
         if (rho > opt.min_relative_decrease) {
           accepted = true;
-          std::swap(poses.p, poses2.p);
-          std::swap(cams.p, cams2.p);
-          std::swap(points.p, points2.p);
+          std::swap(poses.p, poses2.p); std::swap(cams.p, cams2.p); std::swap(points.p, points2.p);
           if (V.sens_off) std::swap(sensors.p, sensors2.p);
           V.poses = poses.p; V.cams = cams.p; V.points = points.p; V.sensors = sensors.p;
           const double t = 2.0 * rho - 1.0;
@@ -4374,19 +4435,16 @@ struct Solver {
           need_linearize = true;
           if (opt.function_tolerance > 0 && std::fabs(cost - new_cost) <= opt.function_tolerance * cost) {
             log(out, new_cost, radius, lin_iters);
-            out->termination_type = BA_CONVERGENCE;
-            out->num_iterations = iter + 1;
+            terminate(BA_CONVERGENCE, iter + 1);
             break;
           }
         } else {
-          radius /= decrease_factor;
-          decrease_factor *= 2.0;
+          decrease_radius();
         }
       }
       log(out, accepted ? new_cost : cost, radius, lin_iters);
       if (radius < opt.min_trust_region_radius) {
-        out->termination_type = BA_CONVERGENCE;
-        out->num_iterations = iter + 1;
+        terminate(BA_CONVERGENCE, iter + 1);
         break;
       }
       if (user_stop(iter + 1, accepted ? new_cost : cost, accepted ? cost - new_cost : 0.0, accepted, radius, lin_iters)) break;
@@ -4395,36 +4453,10 @@ struct Solver {
     out->final_cost = scalar_sum(S_NEWCOST);
     out->lm_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     out->factor_seconds = factor_ms * 1e-3;
-    BA_LAUNCH(ba_renorm_quat_kernel, dim3(grid_for(V.n_poses, 128)), dim3(128), st, V, poses.p);
-    if (comm.world > 1 && comm.by_point) {
-      // every rank moved its own points only: zero the others' variable points and sum over ranks
-      BA_LAUNCH(ba_keep_own_points_kernel, dim3(grid_for(V.n_points, 128)), dim3(128), st, V, comm.rank, comm.world, points.p);
-      comm.allreduce(points.p, 3 * (size_t)V.n_points, st);
-    }
-    if (V.sens_off) {
-      BA_LAUNCH(ba_renorm_sensor_quat_kernel, dim3(grid_for(V.n_sensors, 128)), dim3(128), st, V, sensors.p);
-      std::vector<double> hs(sensors.n);
-      BA_HIP(hipMemcpyAsync(hs.data(), sensors.p, sizeof(double) * sensors.n, hipMemcpyDeviceToHost, st));
-      BA_HIP(hipStreamSynchronize(st));
-      for (int sidx = 0; sidx < prob.num_sensors; ++sidx)
-        if (h_sens_off[sidx] >= 0)
-          std::memcpy(prob.sensors + 7 * (size_t)sidx, hs.data() + 7 * (size_t)sidx, 7 * sizeof(double));
-    }
-    // write back variable blocks only (constant blocks stay bit-identical)
-    std::vector<double> hp(poses.n), hc(cams.n), hx(points.n);
-    BA_HIP(hipMemcpyAsync(hp.data(), poses.p, sizeof(double) * poses.n, hipMemcpyDeviceToHost, st));
-    BA_HIP(hipMemcpyAsync(hc.data(), cams.p, sizeof(double) * cams.n, hipMemcpyDeviceToHost, st));
-    BA_HIP(hipMemcpyAsync(hx.data(), points.p, sizeof(double) * points.n, hipMemcpyDeviceToHost, st));
-    BA_HIP(hipStreamSynchronize(st));
-    for (int i = 0; i < prob.num_poses; ++i)
-      if (h_pose_off[i] >= 0) std::memcpy(prob.poses + 7 * (size_t)i, hp.data() + 7 * (size_t)i, 7 * sizeof(double));
-    for (int k = 0; k < prob.num_cams; ++k)
-      if (h_cam_off[k] >= 0)
-        std::memcpy(prob.cams + BA_CAM_STRIDE * (size_t)k, hc.data() + BA_CAM_STRIDE * (size_t)k,
-                    BA_CAM_STRIDE * sizeof(double));
-    for (int j = 0; j < prob.num_points; ++j)
-      if (h_pt_off[j] >= 0) std::memcpy(prob.points + 3 * (size_t)j, hx.data() + 3 * (size_t)j, 3 * sizeof(double));
+    write_back();
   }
+
+  int estimate_covariance(const ba_covariance_options& co, CovHandle& h);  // (below, with its kernels)
 
   void log(ba_result* out, double c, double rad, int lin) {
     if (out->log_cost && out->num_logged < opt.max_log) {
@@ -4495,19 +4527,13 @@ struct CovHandle {
   int j0 = 0;                    // first 64-block column of X that was inverted
   double* X = nullptr;           // rows / columns [64 j0, n) of L^-1 (device, (n - 64 j0)^2), lower triangular
   double* scale = nullptr;       // [n] Jacobi scales of the rows of X (device; 1 on the padding)
-  hipStream_t st = nullptr;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
+  Stream st;
+  Event ev_a, ev_b;
   std::vector<int> pose_off, pose_dim, cam_off, cam_dim, sens_off, sens_dim;  // offsets in X, -1: no result
   std::vector<double> point_cov;  // [num_points][9]
   std::vector<char> point_has;
   double form_ms = 0.0, factor_ms = 0.0, inverse_ms = 0.0, extract_ms = 0.0;
-  ~CovHandle() {
-    if (X) (void)hipFree(X);
-    if (scale) (void)hipFree(scale);
-    if (ev_a) (void)hipEventDestroy(ev_a);
-    if (ev_b) (void)hipEventDestroy(ev_b);
-    if (st) (void)hipStreamDestroy(st);
-  }
+  ~CovHandle() { if (X) (void)hipFree(X); if (scale) (void)hipFree(scale); }
 };
 
 double elapsed_ms(hipEvent_t a, hipEvent_t b) {
@@ -4520,59 +4546,49 @@ double elapsed_ms(hipEvent_t a, hipEvent_t b) {
 // Sets up the solver's linearisation at the current parameters (Jacobi scales from the same Jacobian, as the LM loop's
 // first iteration), then points, formation, factorisation and triangular inverse. Returns BA_COV_OK or
 // BA_COV_NOT_ESTIMABLE (g_ba_error holds the message); throws on errors.
-int estimate_covariance(Solver& s, const ba_covariance_options& co, CovHandle& h) {
-  const ba_problem& p = s.prob;
+int Solver::estimate_covariance(const ba_covariance_options& co, CovHandle& h) {
+  const ba_problem& p = prob;
   h.mode = co.params;
   h.pose_off.assign(p.num_poses, -1); h.pose_dim.assign(p.num_poses, 0);
   h.cam_off.assign(p.num_cams, -1); h.cam_dim.assign(p.num_cams, 0);
   h.sens_off.assign(std::max(p.num_sensors, 0), -1); h.sens_dim.assign(std::max(p.num_sensors, 0), 0);
   h.point_cov.assign(9 * (size_t)std::max(p.num_points, 0), 0.0);
   h.point_has.assign(std::max(p.num_points, 0), 0);
-  BA_HIP(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-  for (hipEvent_t* e : {&s.ev0, &s.ev1, &s.ev2, &s.ev3}) BA_HIP(hipEventCreate(e));
   ba_result dummy{};
-  if (s.build(&dummy) == 0) return BA_COV_OK;  // no variable block is observed: every query has no result
-  View& V = s.V;
-  const int nc = V.n_c, np = V.n_p;
-  const hipStream_t st = s.st;
-  BA_LAUNCH(ba_scale_kernel, dim3(std::max(grid_for(nc, 256), 1)), dim3(256), st, nc, s.diag_c.p, 0, s.scale_c.p);
-  BA_LAUNCH(ba_scale_kernel, dim3(std::max(grid_for(np, 256), 1)), dim3(256), st, np, s.diag_p.p, 0, s.scale_p.p);
-  s.launch_linearize(true, s.poses.p, s.cams.p, s.points.p, s.sensors.p, S_COST);
-  s.gradient_and_diag();
-  BA_LAUNCH(ba_scale_kernel, dim3(std::max(grid_for(nc, 256), 1)), dim3(256), st, nc, s.diag_c.p, s.opt.jacobi_scaling, s.scale_c.p);
-  BA_LAUNCH(ba_scale_kernel, dim3(std::max(grid_for(np, 256), 1)), dim3(256), st, np, s.diag_p.p, s.opt.jacobi_scaling, s.scale_p.p);
-  s.launch_linearize(true, s.poses.p, s.cams.p, s.points.p, s.sensors.p, S_COST);
-  s.gradient_and_diag();
+  if (build(&dummy) == 0) return BA_COV_OK;  // no variable block is observed: every query has no result
+  const int nc = V.n_c;
+  set_scales(0);
+  initial_linearization();
   // 1. points
   Buf<double> pcov;
   pcov.alloc(9 * (size_t)std::max(p.num_points, 1));
   if (p.num_points > 0)
-    BA_LAUNCH(ba_cov_point_kernel, dim3(grid_for(p.num_points, 128)), dim3(128), st, V, s.Craw.p, co.damping, s.Cinv.p, pcov.p);
+    BA_LAUNCH(ba_cov_point_kernel, dim3(grid_for(p.num_points, 128)), dim3(128), st, V, Craw.p, co.damping, Cinv.p, pcov.p);
   if (co.params != BA_COV_POSES) {
     BA_HIP(hipMemcpyAsync(h.point_cov.data(), pcov.p, sizeof(double) * h.point_cov.size(), hipMemcpyDeviceToHost, st));
     BA_HIP(hipStreamSynchronize(st));
-    for (int j = 0; j < p.num_points; ++j) h.point_has[j] = s.h_pt_off[j] >= 0;
+    for (int j = 0; j < p.num_points; ++j) h.point_has[j] = h_pt_off[j] >= 0;
   }
   if (co.params == BA_COV_POINTS || nc == 0) return BA_COV_OK;
   // 2. the camera-side order of the covariance system: others (intrinsics, then sensor_from_rig blocks, in the solver's
   // order) padded with identity rows to a multiple of 64, then the poses
   std::vector<int> pdim(p.num_poses, 0), cdim(p.num_cams, 0);
-  BA_HIP(hipMemcpy(pdim.data(), s.pose_dim.p, sizeof(int) * pdim.size(), hipMemcpyDeviceToHost));
-  BA_HIP(hipMemcpy(cdim.data(), s.cam_dim.p, sizeof(int) * cdim.size(), hipMemcpyDeviceToHost));
+  BA_HIP(hipMemcpy(pdim.data(), pose_dim.p, sizeof(int) * pdim.size(), hipMemcpyDeviceToHost));
+  BA_HIP(hipMemcpy(cdim.data(), cam_dim.p, sizeof(int) * cdim.size(), hipMemcpyDeviceToHost));
   int n_pd = 0;
-  for (int i = 0; i < p.num_poses; ++i) n_pd += s.h_pose_off[i] >= 0 ? pdim[i] : 0;
+  for (int i = 0; i < p.num_poses; ++i) n_pd += h_pose_off[i] >= 0 ? pdim[i] : 0;
   const int n_o = nc - n_pd;  // the solver's layout: poses [0, n_pd), then intrinsics and sensors
   const int n_op = (n_o + 63) / 64 * 64;
   const int n = n_op + n_pd;
   if (n > 32768)
     throw std::runtime_error("covariance: camera-side dimension " + std::to_string(n) + " exceeds the limit of 32768");
   auto remap = [&](int off) { return off < 0 ? -1 : (off < n_pd ? off + n_op : off - n_pd); };
-  std::vector<int> npose(p.num_poses), ncam(p.num_cams), nsens(s.h_sens_off.size());
-  for (int i = 0; i < p.num_poses; ++i) npose[i] = remap(s.h_pose_off[i]);
-  for (int k = 0; k < p.num_cams; ++k) ncam[k] = remap(s.h_cam_off[k]);
-  for (size_t k = 0; k < nsens.size(); ++k) nsens[k] = remap(s.h_sens_off[k]);
+  std::vector<int> npose(p.num_poses), ncam(p.num_cams), nsens(h_sens_off.size());
+  for (int i = 0; i < p.num_poses; ++i) npose[i] = remap(h_pose_off[i]);
+  for (int k = 0; k < p.num_cams; ++k) ncam[k] = remap(h_cam_off[k]);
+  for (size_t k = 0; k < nsens.size(); ++k) nsens[k] = remap(h_sens_off[k]);
   std::vector<double> sc_old(std::max(nc, 1)), sc(n, 1.0);
-  BA_HIP(hipMemcpyAsync(sc_old.data(), s.scale_c.p, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
+  BA_HIP(hipMemcpyAsync(sc_old.data(), scale_c.p, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
   BA_HIP(hipStreamSynchronize(st));
   for (int i = 0; i < nc; ++i) sc[remap(i)] = sc_old[i];
   Buf<int> d_pose, d_cam, d_sens, d_po, d_so;
@@ -4580,55 +4596,39 @@ int estimate_covariance(Solver& s, const ba_covariance_options& co, CovHandle& h
   if (!nsens.empty()) d_sens.upload(nsens);
   BA_HIP(hipMalloc(reinterpret_cast<void**>(&h.scale), sizeof(double) * n));
   BA_HIP(hipMemcpy(h.scale, sc.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-  if (s.use_priors()) {
-    std::vector<int> po(s.Q.n), so(s.Q.n);
-    BA_HIP(hipMemcpy(po.data(), s.Q.po, sizeof(int) * s.Q.n, hipMemcpyDeviceToHost));
-    BA_HIP(hipMemcpy(so.data(), s.Q.so, sizeof(int) * s.Q.n, hipMemcpyDeviceToHost));
-    for (int k = 0; k < s.Q.n; ++k) { po[k] = remap(po[k]); so[k] = remap(so[k]); }
+  if (use_priors()) {
+    std::vector<int> po(Q.n), so(Q.n);
+    BA_HIP(hipMemcpy(po.data(), Q.po, sizeof(int) * Q.n, hipMemcpyDeviceToHost));
+    BA_HIP(hipMemcpy(so.data(), Q.so, sizeof(int) * Q.n, hipMemcpyDeviceToHost));
+    for (int k = 0; k < Q.n; ++k) { po[k] = remap(po[k]); so[k] = remap(so[k]); }
     d_po.upload(po); d_so.upload(so);
   }
-  BA_HIP(hipDeviceSynchronize());  // (uploads on the NULL stream)
-  s.chol_info.alloc(2);
-  ba_explicit::FormArgs fa = s.form_args();
+  prepare_exact(n);
+  ba_explicit::FormArgs fa = form_args();
   fa.n_c = n;
   fa.pose_off = d_pose.p; fa.cam_off = d_cam.p;
   fa.sens_off = V.sens_off ? d_sens.p : nullptr;
-  if (dev_switch_int("COLMAP_AMD_BA_FORM_PAIRS", 1) != 0 && ba_explicit::build_pair_lists(fa, s.pair_lists, st))
-    fa.pairs = &s.pair_lists;
-  s.Sdense.alloc((size_t)n * n + n);
-  ba_explicit::Workspace ws;
-  s.chol_linv.alloc(ws.linv_doubles(n)); s.chol_tmp.alloc(n);
+  BA_HIP(hipDeviceSynchronize());  // (uploads and memsets on the NULL stream)
+  build_pair_lists(fa);
   Buf<double> zrhs, xsol, piv;
   zrhs.alloc(n); xsol.alloc(n); piv.alloc(n);
   BA_HIP(hipDeviceSynchronize());
-  BA_HIP(hipEventRecord(s.ev2, st));
-  ba_explicit::form(fa, s.Sdense.p, st);
-  if (s.use_priors())
-    ba_explicit::add_prior_rows(s.Sdense.p, n, s.Q.J, d_po.p, d_so.p, s.Q.pdim, s.Q.n, fa.fixed_point, fa.bad, st);
-  ba_explicit::finish(s.Sdense.p, n, fa.fixed_point, fa.bad, st);
+  BA_HIP(hipEventRecord(ev2, st));
+  form_reduced_system(fa, d_po.p, d_so.p);
   if (n_op > 0)
-    BA_LAUNCH(ba_cov_diag_kernel, dim3(grid_for(n_op, 256)), dim3(256), st, s.Sdense.p, n, n_o, n_op,
+    BA_LAUNCH(ba_cov_diag_kernel, dim3(grid_for(n_op, 256)), dim3(256), st, Sdense.p, n, n_o, n_op,
               co.params == BA_COV_ALL ? 0.0 : co.damping, h.scale);
-  BA_HIP(hipEventRecord(s.ev3, st));
+  BA_HIP(hipEventRecord(ev3, st));
   // 3. factorisation (the right-hand side is zero; its solution is not used)
-  ws.Linv = s.chol_linv.p; ws.tmp = s.chol_tmp.p; ws.info = s.chol_info.p;
-  if (dev_switch_int("COLMAP_AMD_BA_CHOL_LOOKAHEAD", 1) != 0) {
-    int prio_least = 0, prio_greatest = 0;
-    BA_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    BA_HIP(hipStreamCreateWithPriority(&s.st_chol, hipStreamNonBlocking, prio_least));
-    BA_HIP(hipEventCreateWithFlags(&s.ev_chol_panel, hipEventDisableTiming));
-    BA_HIP(hipEventCreateWithFlags(&s.ev_chol_u2, hipEventDisableTiming));
-    ws.st2 = s.st_chol; ws.ev_panel = s.ev_chol_panel; ws.ev_u2 = s.ev_chol_u2;
-  }
+  open_cholesky_lookahead();
   double fms = 0.0;
-  ba_explicit::factor_solve(s.Sdense.p, n, zrhs.p, xsol.p, ws, st, s.ev0, s.ev1, &fms);
-  h.form_ms = elapsed_ms(s.ev2, s.ev3);
-  h.factor_ms = fms;
-  BA_LAUNCH(ba_cov_pivot_kernel, dim3(grid_for(n, 256)), dim3(256), st, s.Sdense.p, n, h.scale, piv.p);
+  ba_explicit::factor_solve(Sdense.p, n, zrhs.p, xsol.p, cholesky_workspace(), st, ev0, ev1, &fms);
+  h.form_ms = elapsed_ms(ev2, ev3); h.factor_ms = fms;
+  BA_LAUNCH(ba_cov_pivot_kernel, dim3(grid_for(n, 256)), dim3(256), st, Sdense.p, n, h.scale, piv.p);
   std::vector<double> d(n);
   int info[2] = {0, 0};
   BA_HIP(hipMemcpyAsync(d.data(), piv.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-  BA_HIP(hipMemcpyAsync(info, s.chol_info.p, sizeof(info), hipMemcpyDeviceToHost, st));
+  BA_HIP(hipMemcpyAsync(info, chol_info.p, sizeof(info), hipMemcpyDeviceToHost, st));
   BA_HIP(hipStreamSynchronize(st));
   // 4. rank: the columns of the matrix whose inverse is returned (with eliminated others, the poses only)
   int cols = 0, rank = 0;
@@ -4652,10 +4652,10 @@ int estimate_covariance(Solver& s, const ba_covariance_options& co, CovHandle& h
   h.j0 = co.params == BA_COV_ALL ? 0 : n_op / 64;
   const size_t nx = (size_t)(n - 64 * h.j0);  // only the inverted trailing part is stored
   BA_HIP(hipMalloc(reinterpret_cast<void**>(&h.X), sizeof(double) * std::max<size_t>(nx * nx, 1)));
-  BA_HIP(hipEventRecord(s.ev2, st));
-  ba_explicit::tri_inverse(s.Sdense.p, n, h.j0, s.chol_linv.p, h.X, st);
-  BA_HIP(hipEventRecord(s.ev3, st));
-  h.inverse_ms = elapsed_ms(s.ev2, s.ev3);
+  BA_HIP(hipEventRecord(ev2, st));
+  ba_explicit::tri_inverse(Sdense.p, n, h.j0, chol_linv.p, h.X, st);
+  BA_HIP(hipEventRecord(ev3, st));
+  h.inverse_ms = elapsed_ms(ev2, ev3);
   for (int i = 0; i < p.num_poses; ++i)
     if (npose[i] >= 0) { h.pose_off[i] = npose[i]; h.pose_dim[i] = pdim[i]; }
   if (co.params == BA_COV_ALL) {
@@ -4665,6 +4665,15 @@ int estimate_covariance(Solver& s, const ba_covariance_options& co, CovHandle& h
       if (nsens[k] >= 0) { h.sens_off[k] = nsens[k]; h.sens_dim[k] = 6; }
   }
   return BA_COV_OK;
+}
+
+// gpu_index < 0: the calling thread's current device
+void select_device(int gpu_index) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    throw std::runtime_error("no HIP device available: the MI355X bundle-adjustment backend has no CPU fallback");
+  if (gpu_index >= ndev) throw std::runtime_error("gpu_index out of range");
+  if (gpu_index >= 0) BA_HIP(hipSetDevice(gpu_index));
 }
 
 bool cov_block(const CovHandle& h, int kind, int index, int* off, int* dim) {
@@ -4719,11 +4728,7 @@ static int SolveImpl(ba_problem* problem, const ba_options* options, int32_t gpu
     std::memset(result, 0, sizeof(*result));
     result->log_cost = lc; result->log_radius = lr; result->log_linear_iters = ll;
     result->termination_type = BA_FAILURE;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-      throw std::runtime_error("no HIP device available: the MI355X bundle-adjustment backend has no CPU fallback");
-    if (gpu_index >= ndev) throw std::runtime_error("gpu_index out of range");
-    if (gpu_index >= 0) BA_HIP(hipSetDevice(gpu_index));
+    select_device(gpu_index);
     Comm comm;
     if (c) {
       if (c->world_size < 1 || c->rank < 0 || c->rank >= c->world_size) throw std::runtime_error("bad rank / world_size");
@@ -4844,11 +4849,7 @@ int ba_estimate_covariance(const ba_problem* problem, const ba_options* options,
     if (cov_options->params < BA_COV_POSES || cov_options->params > BA_COV_ALL)
       throw std::runtime_error("ba_covariance_options.params");
     if (!(cov_options->damping >= 0.0)) throw std::runtime_error("ba_covariance_options.damping must be >= 0");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-      throw std::runtime_error("no HIP device available: the MI355X bundle-adjustment backend has no CPU fallback");
-    if (gpu_index >= ndev) throw std::runtime_error("gpu_index out of range");
-    if (gpu_index >= 0) BA_HIP(hipSetDevice(gpu_index));
+    select_device(gpu_index);
     auto cov = std::make_unique<ba_covariance>();
     CovHandle& h = cov->h;
     BA_HIP(hipGetDevice(&h.device));
@@ -4857,12 +4858,10 @@ int ba_estimate_covariance(const ba_problem* problem, const ba_options* options,
       Comm comm;
       // the solver only reads the problem here: it uploads copies and never writes back
       Solver s(*const_cast<ba_problem*>(problem), *options, comm);
-      rc = estimate_covariance(s, *cov_options, h);
+      rc = s.estimate_covariance(*cov_options, h);
     }
     if (rc != BA_COV_OK) return rc;
-    BA_HIP(hipStreamCreateWithFlags(&h.st, hipStreamNonBlocking));
-    BA_HIP(hipEventCreate(&h.ev_a));
-    BA_HIP(hipEventCreate(&h.ev_b));
+    h.st.create(); h.ev_a.create(); h.ev_b.create();
     *out = cov.release();
     return BA_COV_OK;
   } catch (const std::exception& e) {
