@@ -1,5 +1,5 @@
 """pycolmap-style pipeline functions on the MI355X paths: `from colmap_amd.pipeline import
-patch_match_stereo, stereo_fusion, bundle_adjustment`."""
+patch_match_stereo, stereo_fusion, bundle_adjustment, undistort_images`."""
 # ---------------------------------------------------------------------------------------------
 # pycolmap-style pipeline functions (reference pycolmap/pipeline/mvs.cc:119-127,182-193,
 # pycolmap/pipeline/sfm.cc:153-161,258-263): same names, argument order and defaults. Imports are
@@ -51,3 +51,25 @@ def estimate_ba_covariance(options, reconstruction, bundle_adjuster):
     on the GPU; None when they are not estimable."""
     from . import estimators
     return estimators.EstimateBACovariance(options, reconstruction, bundle_adjuster)
+
+
+def undistort_images(output_path, input_path, image_path, image_names=None, output_type="COLMAP", copy_policy="copy",
+                     num_patch_match_src_images=20, undistort_options=None):
+    """pycolmap.undistort_images (pycolmap/pipeline/images.cc): undistorts the images of the sparse model at input_path
+    into a dense workspace at output_path (needs an MI355X). Only the COLMAP output type is part of this package."""
+    import os
+    from . import undistortion, workspace
+    if output_type != "COLMAP":
+        raise ValueError("Invalid `output_type` - supported value is 'COLMAP'.")
+    model = workspace.read_sparse_model(str(input_path))
+    ids = []
+    if image_names:
+        by_name = {img.name: iid for iid, img in model.images.items()}
+        ids = [by_name[n] for n in image_names if n in by_name]
+    os.makedirs(str(output_path), exist_ok=True)
+    opts = undistortion.COLMAPUndistorterOptions(num_patch_match_src_images=num_patch_match_src_images,
+                                                 copy_type=str(copy_policy).lower().replace("_", "-"), image_ids=ids)
+    ctl = undistortion.COLMAPUndistorter(opts, undistort_options or undistortion.UndistortCameraOptions(), model,
+                                         str(image_path), str(output_path))
+    ctl.Run()
+    return ctl
