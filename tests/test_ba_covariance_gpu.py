@@ -194,7 +194,6 @@ def test_crossing_panels():
     case_crossing_panels()
 
 
-@pytest.mark.gpu
 def _mixed_models_problem():
     fp = _flat_problem(120, 900, 6, seed=11, mixed=True)
     for k in range(1, len(fp.cams), 2):  # PINHOLE (f, f, cx, cy) -> OPENCV with zero distortion, refined

@@ -17,6 +17,7 @@ import subprocess
 
 import pytest
 
+import ba_explicit_cases as X
 import test_ba_gpu as G
 from colmap_amd import estimators as est
 
@@ -110,165 +111,19 @@ def test_rigs_priors_and_robust_loss():
 
 
 # ------------------------------------------------------------------------------------------------
-# the explicit formation called directly (ba_schur_explicit.h is an internal C++ interface: mangled names)
+# ba_schur_explicit.h called directly (an internal C++ interface: mangled names): the case functions of
+# tests/ba_explicit_cases.py on host buffers; tests/test_ba_explicit_gpu.py runs the same cases on the hipcc build
 # ------------------------------------------------------------------------------------------------
 
-class _FormArgs(C.Structure):
-    _fields_ = [("n_obs", C.c_int), ("n_points", C.c_int), ("n_c", C.c_int), ("n_poses", C.c_int), ("kd", C.c_int)] + \
-               [(n, C.c_void_p) for n in ("Jpose", "Jcam", "Jsens", "Jpt", "Cinv", "a2c", "pt_ptr", "pt_off", "a_pose", "a_cam",
-                                          "a_pt", "pairs", "a_sensor", "pose_off", "pose_dim", "cam_off", "cam_dim", "sens_off")] + \
-               [("fixed_point", C.c_bool), ("bad", C.c_void_p)]
-
-
-class _Workspace(C.Structure):
-    _fields_ = [("Linv", C.c_void_p), ("tmp", C.c_void_p), ("info", C.c_void_p), ("st2", C.c_void_p),
-                ("ev_panel", C.c_void_p), ("ev_u2", C.c_void_p), ("min_rows128", C.c_int)]
-
-
-class _PairLists(C.Structure):
-    _fields_ = [("inc", C.c_void_p), ("n_inc", C.c_longlong), ("rec", C.c_void_p), ("rec_doubles", C.c_size_t)]
-
-
-def _explicit_entry_points(pairs=False):
-    L = _emul_lib()
-    names = subprocess.run(["nm", "-D", "--defined-only", L._name], capture_output=True, text=True, check=True).stdout.split()
-    pick = lambda key: getattr(L, next(n for n in names if key in n))
-    if pairs:
-        build, free = pick("ba_explicit16build_pair_listsE"), pick("ba_explicit15free_pair_listsE")
-        build.restype = C.c_bool
-        return build, free
-    return pick("ba_explicit4formE"), pick("ba_explicit6finishE"), pick("ba_explicit12factor_solveE")
+def _host():
+    return X.HostBuffers(_emul_lib())
 
 
 @pytest.mark.parametrize("scale,expect_bad", [(0.1, False), (100.0, True)])
 def test_fixed_point_formation_and_its_overflow_flag(scale, expect_bad):
-    """form_kernel<.., FIXED> on two observations of one point in two pose blocks against numpy:
-    S = sum_ab J_a^T (delta_ab I - E_a C^-1 E_b^T) J_b, accumulated in 2^-60 fixed point. With columns scaled as Jacobi
-    scaling leaves them (|term| < 1) the matrix is exact to the quantum; a term the fixed point cannot hold raises
-    FormArgs::bad, finish() poisons S[0][0] and the factorisation answers NaN (the LM loop rejects such a step) --
-    the integer conversion alone would have produced a finite, wrong matrix."""
-    import numpy as np
-    form, finish, factor_solve = _explicit_entry_points()
-    rng = np.random.default_rng(5)
-    N, n_c = 2, 12
-    Jpose = (scale * rng.uniform(-1, 1, (12, N)))          # c-order planes [2 * 6][N]
-    Jpt = (scale * rng.uniform(-1, 1, (6, N)))             # p-order planes [2 * 3][N]
-    E = [np.array([[Jpt[r * 3 + m, a] for m in range(3)] for r in range(2)]) for a in range(N)]
-    Cinv = np.linalg.inv(sum(e.T @ e for e in E) + 0.5 * scale * scale * np.eye(3))
-    ints = lambda v: np.ascontiguousarray(v, np.int32)
-    arrs = dict(Jpose=np.ascontiguousarray(Jpose), Jcam=np.zeros((8, N)), Jpt=np.ascontiguousarray(Jpt),
-                Cinv=np.ascontiguousarray(Cinv.reshape(1, 9)), a2c=ints([0, 1]), pt_ptr=ints([0, 2]), pt_off=ints([0]),
-                a_pose=ints([0, 1]), a_cam=ints([0, 0]), pose_off=ints([0, 6]), pose_dim=ints([6, 6]), cam_off=ints([-1]),
-                cam_dim=ints([0]))
-    bad = np.zeros(1, np.int32)
-    fa = _FormArgs(n_obs=N, n_points=1, n_c=n_c, kd=4, fixed_point=True, bad=bad.ctypes.data)
-    for k, v in arrs.items():
-        setattr(fa, k, v.ctypes.data)
-    S = np.full((n_c + 1, n_c), 7.0)  # (n_c + 1 rows: factor_solve's buffer)
-    form(C.byref(fa), S.ctypes.data_as(C.c_void_p), None)
-    finish(S.ctypes.data_as(C.c_void_p), C.c_int(n_c), C.c_bool(True), bad.ctypes.data_as(C.c_void_p), None)
-    J = [np.array([[Jpose[r * 6 + d, a] for d in range(6)] for r in range(2)]) for a in range(N)]
-    want = np.zeros((n_c, n_c))
-    for a in range(N):
-        for b in range(N):
-            M = (np.eye(2) if a == b else 0.0) - E[a] @ Cinv @ E[b].T
-            want[6 * a:6 * a + 6, 6 * b:6 * b + 6] += J[a].T @ M @ J[b]
-    assert bool(bad[0]) == expect_bad
-    if not expect_bad:
-        low = np.tril_indices(n_c)
-        assert np.abs(want).max() < 1.0
-        np.testing.assert_allclose(S[low], want[low], rtol=0, atol=144 * 2.0 ** -60 + 1e-17)
-        return
-    assert np.isnan(S[0, 0])
-    x, rhs = np.zeros(n_c), np.ones(n_c)
-    linv, tmp, info = np.zeros(64 * 64), np.zeros(n_c), np.zeros(1, np.int32)
-    ws = _Workspace(Linv=linv.ctypes.data, tmp=tmp.ctypes.data, info=info.ctypes.data, min_rows128=12 * 128)
-    factor_solve(S.ctypes.data_as(C.c_void_p), C.c_int(n_c), rhs.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p),
-                 C.byref(ws), None, None, None, None)
-    assert info[0] == 1 and np.isnan(x).all()
-
-
-def _random_formation_problem(seed, n_poses, n_points, shared_cams, rigs):
-    """A random linearisation in the layouts FormArgs describes (c-order planes, p-order point columns, p-order
-    topology) with constant poses / cameras / points, tracks of 1-7 observations, optionally cameras shared between
-    images and rig frames (several images per pose block, each with its own sensor_from_rig block)."""
-    import numpy as np
-    rng = np.random.default_rng(seed)
-    n_cams = 2 if shared_cams else n_poses
-    n_sens = 3 if rigs else 0
-    obs = []  # (point, pose, cam, sensor)
-    for j in range(n_points):
-        t = int(rng.integers(1, 8))
-        images = set()
-        while len(images) < t:
-            pose = int(rng.integers(n_poses))
-            sens = int(rng.integers(n_sens)) if rigs else -1
-            images.add((pose, sens))
-        for pose, sens in sorted(images):
-            obs.append((j, pose, pose % n_cams, sens))
-    N = len(obs)
-    perm = rng.permutation(N)  # p-order slot a -> c-order slot
-    off = 0
-    pose_off, pose_dim = [], []
-    for i in range(n_poses):
-        d = [6, 6, 6, 5, 0][int(rng.integers(5))]
-        pose_dim.append(d); pose_off.append(off if d else -1); off += d
-    cam_off, cam_dim = [], []
-    for i in range(n_cams):
-        d = [2, 3, 0][int(rng.integers(3))]
-        cam_dim.append(d); cam_off.append(off if d else -1); off += d
-    sens_off = []
-    for i in range(n_sens):
-        v = bool(rng.integers(2))
-        sens_off.append(off if v else -1); off += 6 if v else 0
-    n_c = off
-    pt_off = [(-1 if rng.integers(5) == 0 else 3 * j) for j in range(n_points)]
-    scale = 0.08
-    Jpose, Jcam, Jsens = (scale * rng.uniform(-1, 1, (12, N)) for _ in range(3))
-    Jcam = scale * rng.uniform(-1, 1, (8, N))
-    Jpt = scale * rng.uniform(-1, 1, (6, N))
-    pt_ptr = np.zeros(n_points + 1, np.int32)
-    for j, *_ in obs:
-        pt_ptr[j + 1] += 1
-    pt_ptr = np.cumsum(pt_ptr).astype(np.int32)
-    Cinv = np.zeros((n_points, 9))
-    want = np.zeros((n_c, n_c))
-    for j in range(n_points):
-        sl = range(pt_ptr[j], pt_ptr[j + 1])
-        E = {a: Jpt[:, a].reshape(2, 3) for a in sl}
-        Ci = np.linalg.inv(sum(E[a].T @ E[a] for a in sl) + 0.01 * np.eye(3))
-        Cinv[j] = Ci.reshape(9)
-        cols = {}
-        for a in sl:
-            _, pose, cam, sens = obs[a]
-            c = perm[a]
-            J, idx = [], []
-            if pose_off[pose] >= 0:
-                for d in range(pose_dim[pose]):
-                    J.append((Jpose[d, c], Jpose[6 + d, c])); idx.append(pose_off[pose] + d)
-            if cam_off[cam] >= 0:
-                for d in range(cam_dim[cam]):
-                    J.append((Jcam[d, c], Jcam[4 + d, c])); idx.append(cam_off[cam] + d)
-            if sens >= 0 and sens_off[sens] >= 0:
-                for d in range(6):
-                    J.append((Jsens[d, c], Jsens[6 + d, c])); idx.append(sens_off[sens] + d)
-            cols[a] = (np.array(J).reshape(-1, 2).T, idx)
-        for a in sl:
-            for b in sl:
-                if pt_off[j] < 0 and a != b:
-                    continue
-                M = (np.eye(2) if a == b else 0.0) - (E[a] @ Ci @ E[b].T if pt_off[j] >= 0 else 0.0)
-                (Ja, ia), (Jb, ib) = cols[a], cols[b]
-                if ia and ib:
-                    want[np.ix_(ia, ib)] += Ja.T @ M @ Jb
-    ints = lambda v: np.ascontiguousarray(v, np.int32)
-    arrs = dict(Jpose=np.ascontiguousarray(Jpose), Jcam=np.ascontiguousarray(Jcam), Jpt=np.ascontiguousarray(Jpt),
-                Cinv=np.ascontiguousarray(Cinv), a2c=ints(perm), pt_ptr=ints(pt_ptr), pt_off=ints(pt_off),
-                a_pose=ints([o[1] for o in obs]), a_cam=ints([o[2] for o in obs]), a_pt=ints([o[0] for o in obs]),
-                pose_off=ints(pose_off), pose_dim=ints(pose_dim), cam_off=ints(cam_off), cam_dim=ints(cam_dim))
-    if rigs:
-        arrs.update(Jsens=np.ascontiguousarray(Jsens), a_sensor=ints([o[3] for o in obs]), sens_off=ints(sens_off))
-    return dict(N=N, n_points=n_points, n_c=n_c, n_poses=n_poses, arrs=arrs, want=want)
+    """form_kernel<.., FIXED> on two observations of one point against numpy, exact to the quantum; a term the fixed
+    point cannot hold raises FormArgs::bad, finish() poisons S[0][0] and the factorisation answers NaN."""
+    X.case_fixed_point_overflow(_host(), scale, expect_bad)
 
 
 @pytest.mark.parametrize("shared_cams,rigs,fixed", [(False, False, True), (True, False, True), (True, True, True),
@@ -279,82 +134,60 @@ def test_pair_major_formation_against_numpy_and_the_point_major_kernel(shared_ca
     frames (several images per pose block: runs of one pair of pose blocks change their targets) -- with constant poses,
     cameras, sensors and points and 5-wide pose blocks: the pair-major formation (records, incidence lists sorted by
     pose pair, one wave per 64 incidences) and the point-major kernel (one atomic per term) against numpy, fixed-point
-    and fp64 accumulation."""
-    import numpy as np
-    form, finish, _ = _explicit_entry_points()
-    build, free = _explicit_entry_points(pairs=True)
-    P = _random_formation_problem(11 + 2 * shared_cams + rigs, n_poses=9, n_points=60, shared_cams=shared_cams, rigs=rigs)
-    bad = np.zeros(1, np.int32)
-    fa = _FormArgs(n_obs=P["N"], n_points=P["n_points"], n_c=P["n_c"], n_poses=P["n_poses"], kd=4, fixed_point=fixed,
-                   bad=bad.ctypes.data)
-    for k, v in P["arrs"].items():
-        setattr(fa, k, v.ctypes.data)
-    n_c, low = P["n_c"], np.tril_indices(P["n_c"])
-    assert np.abs(P["want"]).max() < 1.0
-    got = {}
-    for which in ("points", "pairs"):
-        pl = _PairLists()
-        if which == "pairs":
-            assert build(C.byref(fa), C.byref(pl), None) and pl.n_inc >= P["N"]
-            fa.pairs = C.addressof(pl)
-        S = np.full((n_c, n_c), 7.0)
-        form(C.byref(fa), S.ctypes.data_as(C.c_void_p), None)
-        finish(S.ctypes.data_as(C.c_void_p), C.c_int(n_c), C.c_bool(fixed), bad.ctypes.data_as(C.c_void_p), None)
-        fa.pairs = None
-        free(C.byref(pl))
-        assert bad[0] == 0 and pl.inc is None
-        np.testing.assert_allclose(S[low], P["want"][low], rtol=0, atol=2e-15)
-        got[which] = S[low]
-    np.testing.assert_allclose(got["pairs"], got["points"], rtol=0, atol=1e-15)
+    and fp64 accumulation. Widths 10 and 20 (kd = 4)."""
+    P = X.formation_problem(11 + 2 * shared_cams + rigs, 9, 60, shared_cams, rigs)
+    X.case_formation(_host(), P, fixed, legacy_bars=True)
 
 
-def _factor_solve_directly(A, rhs, min_rows128):
-    import numpy as np
-    _, _, factor_solve = _explicit_entry_points()
-    n = A.shape[0]
-    S = np.full((n + 1, n), 1e300)  # the upper triangle is never read; row n: the right-hand side rides along
-    S[np.tril_indices(n)] = A[np.tril_indices(n)]
-    x = np.zeros(n)
-    linv, tmp, info = np.zeros(((n + 63) // 64) * 64 * 64), np.zeros(n), np.zeros(1, np.int32)
-    ws = _Workspace(Linv=linv.ctypes.data, tmp=tmp.ctypes.data, info=info.ctypes.data, min_rows128=min_rows128)
-    factor_solve(S.ctypes.data_as(C.c_void_p), C.c_int(n), np.ascontiguousarray(rhs).ctypes.data_as(C.c_void_p),
-                 x.ctypes.data_as(C.c_void_p), C.byref(ws), None, None, None, None)
-    return S, linv.reshape(-1, 64, 64), x, int(info[0])
+@pytest.mark.parametrize("kd,rigs,fixed", [(8, False, True), (4, True, False), (16, False, True), (16, True, True),
+                                           (16, True, False)])
+def test_formation_widths_and_chunked_tracks(kd, rigs, fixed):
+    """Widths 14 (kd = 8), 20, 28 (kd = 16, exactly full with a variable sensor) of both formations, with tracks of
+    1 / 2 / 15 / 16 / 17 / 33 observations: form_kernel stages a point 16 observations at a time, so these reach its
+    second and third chunk, and for the constant points with 17 and 33 observations the chunks it skips."""
+    X.case_formation(_host(), X.formation_problem(100 + kd + rigs, 12, 40, True, rigs, kd=kd, long_tracks=True), fixed)
+
+
+@pytest.mark.parametrize("fixed", [True, False])
+def test_prior_rows_and_lm_diagonal(fixed):
+    X.case_prior_rows_and_lm_diagonal(_host(), fixed)
 
 
 @pytest.mark.parametrize("n,min_rows128", [(45, 12 * 128), (64, 12 * 128), (333, 12 * 128), (900, 256)])
 def test_blocked_cholesky_directly_against_numpy(n, min_rows128):
     """factor_solve on a random SPD matrix: the factor, the stored inverses of its diagonal blocks and the solution
-    against numpy. n = 45 / 64: one (short / full) diagonal block -- chol_diag_kernel alone (blocked over 16 x 16 tiles,
-    the inverse of the triangle riding along); 333: six panels, a ragged last block, two outer
-    panels; 900 with the tile threshold lowered: the 128 x 128 trailing update (the columns right of the next outer panel)
-    with its register prefetch, including diagonal tiles and a ragged edge."""
-    import numpy as np
-    rng = np.random.default_rng(n)
-    B = rng.standard_normal((n, n + 8))
-    A = B @ B.T / n + 0.5 * np.eye(n)
-    rhs = rng.standard_normal(n)
-    S, linv, x, info = _factor_solve_directly(A, rhs, min_rows128)
-    assert info == 0
-    L = np.linalg.cholesky(A)
-    low = np.tril_indices(n)
-    np.testing.assert_allclose(S[low], L[low], rtol=0, atol=1e-12)
-    for k in range((n + 63) // 64):
-        kb = min(64, n - 64 * k)
-        blk = L[64 * k:64 * k + kb, 64 * k:64 * k + kb]
-        np.testing.assert_allclose(linv[k][:kb, :kb], np.linalg.inv(blk), rtol=0, atol=1e-11)
-        assert (linv[k][kb:, :] == 0).all() and (linv[k][:, kb:] == 0).all()
-        assert (np.triu(linv[k][:kb, :kb], 1) == 0).all()
-    np.testing.assert_allclose(x, np.linalg.solve(A, rhs), rtol=0, atol=1e-10)
+    against numpy, and the componentwise backward bounds. n = 45 / 64: one (short / full) diagonal block --
+    chol_diag_kernel alone (blocked over 16 x 16 tiles, the inverse of the triangle riding along); 333: six panels, a
+    ragged last block, two outer panels; 900 with the tile threshold lowered: the 128 x 128 trailing update (the columns
+    right of the next outer panel) with its register prefetch, including diagonal tiles and a ragged edge."""
+    X.case_cholesky(_host(), n, min_rows128)
+
+
+@pytest.mark.parametrize("n", [1, 65, 255, 256, 257])
+def test_blocked_cholesky_around_block_and_panel_edges(n):
+    X.case_cholesky(_host(), n)
+
+
+def test_blocked_cholesky_lookahead_call_order():
+    """The two-stream call order (synchronous here: the overlap itself is a GPU test) on three outer panels."""
+    X.case_cholesky(_host(), 600, 256, lookahead=True)
 
 
 def test_blocked_cholesky_reports_a_failed_pivot():
-    import numpy as np
-    n = 100
-    A = np.eye(n)
-    A[70, 70] = -1.0
-    _, _, x, info = _factor_solve_directly(A, np.ones(n), 12 * 128)
-    assert info == 1 and np.isnan(x).all()
+    X.case_failed_pivot(_host(), 100, 70)
+
+
+def test_blocked_cholesky_reports_a_failed_pivot_in_a_later_outer_panel():
+    X.case_failed_pivot(_host(), 300, 270)
+
+
+@pytest.mark.parametrize("n,j0", [(64, 0), (130, 0), (130, 1), (333, 0), (333, 2), (333, 5)])
+def test_tri_inverse_directly(n, j0):
+    X.case_tri_inverse(_host(), n, j0)
+
+
+def test_extract_cov_blocks_directly():
+    X.case_extract_cov_blocks(_host())
 
 
 # ------------------------------------------------------------------------------------------------
