@@ -28,6 +28,7 @@
 //  * S x = (B + D^2) x - E C^-1 E^T x is never formed: three kernels per product.
 #include "../../include/colmap_amd_ba.h"
 #include "../../include/colmap_amd_ba_covariance.h"
+#include "ba_probe.h"
 #include "ba_schur_explicit.h"
 #include "switches.h"
 
@@ -4954,3 +4955,233 @@ void ba_covariance_destroy(ba_covariance* cov) {
 const char* ba_last_error(void) { return g_ba_error.c_str(); }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Step probe (ba_probe.h): the steps of Solver::run()'s first LM iteration one by one, their results copied out in
+// the caller's indexing. Tests only; nothing here launches a kernel or computes.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+template <typename T>
+std::vector<T> probe_fetch(Solver& s, const T* dev, size_t n) {
+  std::vector<T> h(n);
+  BA_HIP(hipStreamSynchronize(s.st));
+  if (n > 0 && dev) BA_HIP(hipMemcpy(h.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost));
+  return h;
+}
+
+// a camera-side device vector into the caller's (n_c entries)
+void probe_cam_vector(Solver& s, const double* dev, double* out) {
+  if (!out || s.V.n_c <= 0) return;
+  const std::vector<double> h = probe_fetch(s, dev, (size_t)s.V.n_c);
+  std::memcpy(out, h.data(), sizeof(double) * h.size());
+}
+
+// a point-side device vector (3 entries at pt_off[j]) into out[3 j ..]
+void probe_point_vector(Solver& s, const double* dev, double* out) {
+  if (!out || s.V.n_p <= 0) return;
+  const std::vector<double> h = probe_fetch(s, dev, (size_t)s.V.n_p);
+  for (int j = 0; j < s.prob.num_points; ++j)
+    if (s.h_pt_off[j] >= 0)
+      for (int c = 0; c < 3; ++c) out[3 * (size_t)j + c] = h[(size_t)s.h_pt_off[j] + c];
+}
+
+void probe_blocks(Solver& s, const double* dev, double* out, int cap) {
+  if (!out || s.moff_total <= 0) return;
+  if (s.moff_total > cap) throw std::runtime_error("ba_probe: block_cap too small");
+  const std::vector<double> h = probe_fetch(s, dev, (size_t)s.moff_total);
+  std::memcpy(out, h.data(), sizeof(double) * h.size());
+}
+
+// The stored Jacobian planes (c-order camera side, p-order point side) as one 2 x BA_PROBE_JCOLS block per caller
+// observation; `o_of_a` = caller observation of p-order slot a
+template <typename JT>
+void probe_jacobian(Solver& s, const JT* Jpose, const JT* Jcam, const double* Jsens, const JT* Jpt,
+                    const std::vector<int64_t>& o_of_a, const std::vector<int>& a2c, JT* out) {
+  if (!out) return;
+  const size_t N = (size_t)s.V.n_obs;
+  const int kd = s.kd;
+  const std::vector<JT> hp = probe_fetch(s, Jpose, 2 * PD * N), hk = probe_fetch(s, Jcam, 2 * (size_t)kd * N),
+                        hx = probe_fetch(s, Jpt, 6 * N);
+  std::vector<double> hs;
+  if (Jsens) hs = probe_fetch(s, Jsens, 12 * N);
+  for (size_t a = 0; a < N; ++a) {
+    const size_t c = (size_t)a2c[a];
+    for (int r = 0; r < 2; ++r) {
+      JT* row = out + ((size_t)o_of_a[a] * 2 + r) * BA_PROBE_JCOLS;
+      for (int k = 0; k < PD; ++k) row[BA_PROBE_POSE_COL + k] = hp[(size_t)(r * PD + k) * N + c];
+      for (int k = 0; k < kd; ++k) row[BA_PROBE_CAM_COL + k] = hk[(size_t)(r * kd + k) * N + c];
+      if (Jsens)
+        for (int k = 0; k < 6; ++k) row[BA_PROBE_SENS_COL + k] = (JT)hs[(size_t)(r * 6 + k) * N + c];
+      for (int k = 0; k < 3; ++k) row[BA_PROBE_PT_COL + k] = hx[(size_t)(r * 3 + k) * N + a];
+    }
+  }
+}
+
+void probe_run(const ba_problem& p_in, const ba_options& opt, ba_probe_io& io) {
+  ba_problem p = p_in;  // (the solver holds a reference; write_back() is never called)
+  Comm comm;
+  Solver s(p, opt, comm);
+  ba_result res{};
+  io.pcg_iterations = 0; io.pcg_pipelined = -1;
+  io.cost = io.s_model = io.s_newcost = 0.0;
+  const int built = s.build(&res);
+  io.n_active = built;
+  if (io.obs_active) std::memset(io.obs_active, 0, (size_t)p.num_obs);
+  if (built == 0) {
+    io.n_c = io.n_p = io.moff_total = 0;
+    return;
+  }
+  const View& V = s.V;
+  const int n = V.n_obs, n_c = V.n_c;
+  if (n_c > io.vec_stride) throw std::runtime_error("ba_probe: vec_stride too small");
+  // ---- path facts
+  io.n_c = n_c; io.n_p = V.n_p; io.moff_total = s.moff_total;
+  io.width_tier = s.width_tier; io.kd = s.kd; io.bd = s.bd; io.plain_model = s.plain_model;
+  io.split_linearize = s.split_linearize ? 1 : 0; io.op32 = s.op32 ? 1 : 0;
+  io.n_tiles = V.n_tiles; io.n_chunks = V.n_chunks; io.n_heavy = s.n_heavy; io.pv_n = s.PV.n;
+  io.rhs_pass_fused = s.rhs_pass_fused() ? 1 : 0; io.n_priors = s.Q.n; io.n_paired = s.n_paired;
+  // ---- maps
+  const std::vector<int> a_pose = probe_fetch(s, V.a_pose, (size_t)n), a_cam = probe_fetch(s, V.a_cam, (size_t)n),
+                         a_pt = probe_fetch(s, V.a_pt, (size_t)n), a2c = probe_fetch(s, V.a2c, (size_t)n),
+                         pose_dim = probe_fetch(s, V.pose_dim, (size_t)p.num_poses),
+                         cam_dim = probe_fetch(s, V.cam_dim, (size_t)p.num_cams),
+                         blk_off = probe_fetch(s, V.blk_off, (size_t)V.n_blk),
+                         blk_moff = probe_fetch(s, V.blk_moff, (size_t)V.n_blk);
+  const std::vector<double> a_xy = probe_fetch(s, V.a_xy, 2 * (size_t)n);
+  // p-order slot -> caller observation: the active observations, stably sorted by point (build()). Checked against
+  // the device's own p-order topology below instead of trusted.
+  std::vector<int64_t> o_of_a;
+  {
+    std::vector<std::vector<int64_t>> by_point((size_t)p.num_points);
+    std::vector<char> cam_variable((size_t)p.num_cams, 0);
+    for (int k = 0; k < p.num_cams; ++k)
+      for (int j = 0; j < num_params_of(p.cam_model[k]); ++j)
+        if (!p.cam_const[(size_t)k * BA_CAM_STRIDE + j]) cam_variable[k] = 1;
+    for (int64_t o = 0; o < p.num_obs; ++o) {
+      const int sv = p.obs_sensor ? p.obs_sensor[o] : -1;
+      const bool sens_var = sv >= 0 && p.sensor_const != nullptr && !p.sensor_const[sv];
+      if (p.pose_const[p.obs_pose[o]] && !cam_variable[p.obs_cam[o]] && p.point_const[p.obs_point[o]] && !sens_var) continue;
+      by_point[(size_t)p.obs_point[o]].push_back(o);
+    }
+    for (const auto& l : by_point) o_of_a.insert(o_of_a.end(), l.begin(), l.end());
+  }
+  if ((int)o_of_a.size() != n) throw std::runtime_error("ba_probe: active observation count");
+  for (int a = 0; a < n; ++a) {
+    const int64_t o = o_of_a[a];
+    if (a_pose[a] != p.obs_pose[o] || a_cam[a] != p.obs_cam[o] || a_pt[a] != p.obs_point[o] ||
+        a_xy[2 * (size_t)a] != p.obs_xy[2 * o] || a_xy[2 * (size_t)a + 1] != p.obs_xy[2 * o + 1])
+      throw std::runtime_error("ba_probe: p-order observation map");
+    if (io.obs_active) io.obs_active[o] = 1;
+  }
+  auto moff_of = [&](int off) {
+    for (int b = 0; b < V.n_blk; ++b)
+      if (blk_off[b] == off) return blk_moff[b];
+    return -1;
+  };
+  for (int i = 0; i < p.num_poses; ++i) {
+    const int off = s.h_pose_off[i];
+    if (io.pose_off) io.pose_off[i] = off;
+    if (io.pose_dim) io.pose_dim[i] = off >= 0 ? pose_dim[i] : -1;
+    if (io.pose_moff) io.pose_moff[i] = off >= 0 ? moff_of(off) : -1;
+  }
+  for (int k = 0; k < p.num_cams; ++k) {
+    const int off = s.h_cam_off[k];
+    if (io.cam_off) io.cam_off[k] = off;
+    if (io.cam_dim) io.cam_dim[k] = off >= 0 ? cam_dim[k] : -1;
+    if (io.cam_moff) io.cam_moff[k] = off >= 0 ? moff_of(off) : -1;
+  }
+  for (int k = 0; k < p.num_sensors; ++k) {
+    const int off = s.h_sens_off[k];
+    if (io.sens_off) io.sens_off[k] = off;
+    if (io.sens_dim) io.sens_dim[k] = off >= 0 ? 6 : -1;
+    if (io.sens_moff) io.sens_moff[k] = off >= 0 ? moff_of(off) : -1;
+  }
+  if (io.pt_off)
+    for (int j = 0; j < p.num_points; ++j) io.pt_off[j] = s.h_pt_off[j];
+
+  // ---- 1. linearisation
+  s.set_scales(0);
+  s.initial_linearization();
+  io.cost = s.scalar(S_COST);
+  {
+    const std::vector<double> hr = probe_fetch(s, V.res, 2 * (size_t)n), hrp = probe_fetch(s, V.res_p, 2 * (size_t)n);
+    for (int a = 0; a < n; ++a)
+      for (int r = 0; r < 2; ++r) {
+        if (io.res) io.res[2 * o_of_a[a] + r] = hr[(size_t)r * n + a2c[a]];
+        if (io.res_p) io.res_p[2 * o_of_a[a] + r] = hrp[(size_t)r * n + a];
+      }
+  }
+  probe_jacobian<double>(s, V.Jpose, V.Jcam, V.sens_off ? V.Jsens : nullptr, V.Jpt, o_of_a, a2c, io.J);
+  if (s.op32) probe_jacobian<float>(s, V.Jpose32, V.Jcam32, nullptr, V.Jpt32, o_of_a, a2c, io.J32);
+  probe_cam_vector(s, s.gc.p, io.gc); probe_cam_vector(s, s.diag_c.p, io.diag_c); probe_cam_vector(s, s.scale_c.p, io.scale_c);
+  probe_point_vector(s, s.gp.p, io.gp); probe_point_vector(s, s.diag_p.p, io.diag_p); probe_point_vector(s, s.scale_p.p, io.scale_p);
+  if (io.Craw) {
+    const std::vector<double> h = probe_fetch(s, s.Craw.p, 6 * (size_t)p.num_points);
+    for (int j = 0; j < p.num_points; ++j)
+      for (int e = 0; e < 6; ++e) io.Craw[6 * (size_t)j + e] = h[(size_t)e * p.num_points + j];
+  }
+
+  // ---- 2. the damped system
+  s.damp(io.radius);
+  probe_cam_vector(s, s.Dc.p, io.Dc);
+  probe_point_vector(s, s.Dp.p, io.Dp);
+  if (io.Cinv) {
+    const std::vector<double> h = probe_fetch(s, s.Cinv.p, 9 * (size_t)p.num_points);
+    for (int j = 0; j < p.num_points; ++j)
+      if (s.h_pt_off[j] >= 0) std::memcpy(io.Cinv + 9 * (size_t)j, h.data() + 9 * (size_t)j, 9 * sizeof(double));
+  }
+  if (n_c > 0) {
+    s.form_preconditioner();
+    probe_blocks(s, s.M.p, io.M, io.block_cap);
+    probe_blocks(s, s.Minv.p, io.Minv, io.block_cap);
+    s.reduced_rhs();
+    probe_cam_vector(s, s.rhs.p, io.rhs);
+    // ---- 3. products with the caller's vectors (s.pdir / s.q as staging: pcg() initialises both)
+    for (int inexact = 0; inexact < 2; ++inexact)
+      for (int i = 0; i < io.num_vectors; ++i) {
+        BA_HIP(hipStreamSynchronize(s.st));
+        BA_HIP(hipMemcpy(s.pdir.p, io.x_in + (size_t)i * io.vec_stride, sizeof(double) * n_c, hipMemcpyHostToDevice));
+        s.schur_multiply(s.pdir.p, s.q.p, inexact != 0);
+        if (io.q_out) probe_cam_vector(s, s.q.p, io.q_out + ((size_t)inexact * io.num_vectors + i) * io.vec_stride);
+      }
+    // ---- 4. the linear solve
+    const long long pipelined_before = g_pcg_pipelined_solves, stepwise_before = g_pcg_stepwise_solves;
+    io.pcg_iterations = s.pcg(opt.max_linear_solver_iterations, opt.eta);
+    io.pcg_pipelined = g_pcg_pipelined_solves > pipelined_before ? 1 : (g_pcg_stepwise_solves > stepwise_before ? 0 : -1);
+    probe_cam_vector(s, s.x.p, io.x);
+  }
+  // ---- 5. the step
+  s.back_substitute_and_model_change();
+  s.evaluate_candidate();
+  {
+    double h[NSCALAR];
+    s.scalars_to_host(h);
+    io.s_model = h[S_MODEL];
+    io.s_newcost = h[S_NEWCOST];
+  }
+  probe_point_vector(s, s.dp.p, io.dp);
+  auto fetch_to = [&](const double* dev, size_t count, double* out) {
+    if (!out || count == 0) return;
+    const std::vector<double> h = probe_fetch(s, dev, count);
+    std::memcpy(out, h.data(), sizeof(double) * count);
+  };
+  fetch_to(s.poses2.p, 7 * (size_t)p.num_poses, io.cand_poses);
+  fetch_to(s.cams2.p, BA_CAM_STRIDE * (size_t)p.num_cams, io.cand_cams);
+  fetch_to(s.points2.p, 3 * (size_t)p.num_points, io.cand_points);
+  if (V.sensors) fetch_to(s.sensors2.p, 7 * (size_t)p.num_sensors, io.cand_sensors);
+}
+
+}  // namespace
+
+extern "C" int ba_probe_steps(const ba_problem* problem, const ba_options* options, int32_t gpu_index, ba_probe_io* io) {
+  try {
+    if (!problem || !options || !io) throw std::runtime_error("null argument");
+    select_device(gpu_index);
+    probe_run(*problem, *options, *io);
+    return 0;
+  } catch (const std::exception& e) {
+    g_ba_error = e.what();
+    return 1;
+  }
+}

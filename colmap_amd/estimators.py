@@ -220,6 +220,7 @@ class BundleAdjustmentSummary:
     lm_seconds: float = 0.0
     log_cost: Optional[np.ndarray] = None
     log_linear_iters: Optional[np.ndarray] = None
+    log_radius: Optional[np.ndarray] = None   # trust-region radius after every logged iteration
     linear_solver_used: int = 0     # ba_result.linear_solver_used: the tier that ran (SOLVER_*)
     factor_seconds: float = 0.0     # exact tiers: time inside the blocked Cholesky
     setup_seconds: float = 0.0      # flattening into the device layout, index lists, upload: everything before the LM loop
@@ -791,7 +792,8 @@ def solve_flat(fp: FlatProblem, so: Optional[SolverOptions] = None, gpu_index: i
         num_effective_parameters=r.num_effective_parameters,
         total_linear_iterations=r.total_linear_iterations, initial_cost=r.initial_cost,
         final_cost=r.final_cost, lm_seconds=r.lm_seconds, log_cost=log_cost[: r.num_logged].copy(),
-        log_linear_iters=log_lin[: r.num_logged].copy(), linear_solver_used=int(r.linear_solver_used),
+        log_linear_iters=log_lin[: r.num_logged].copy(), log_radius=log_radius[: r.num_logged].copy(),
+        linear_solver_used=int(r.linear_solver_used),
         factor_seconds=float(r.factor_seconds), setup_seconds=float(r.setup_seconds))
 
 

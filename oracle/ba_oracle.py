@@ -58,7 +58,8 @@ def solve_fn_fast(p, o, r):
     return lib_fast().bao_solve(p, o, r)
 
 
-def reproj_error(model, point, pose, params, xy, want_jac=True):
+def reproj_error(model, point, pose, params, xy, want_jac=True, use=None):
+    """`use`: the checker build to call (lib() by default; lib_fast() measures a comparison's noise floor)."""
     point = np.ascontiguousarray(point, np.float64)
     pose = np.ascontiguousarray(pose, np.float64)
     prm = np.zeros(16)
@@ -68,7 +69,7 @@ def reproj_error(model, point, pose, params, xy, want_jac=True):
     r = np.zeros(2)
     Jpt, Jpose, Jpar = np.zeros((2, 3)), np.zeros((2, 7)), np.zeros((2, P))
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    lib().bao_reproj_error(C.c_int(model), vp(point), vp(pose), vp(prm), vp(xy), vp(r),
+    (use or lib()).bao_reproj_error(C.c_int(model), vp(point), vp(pose), vp(prm), vp(xy), vp(r),
                            vp(Jpt) if want_jac else None, vp(Jpose) if want_jac else None,
                            vp(Jpar) if want_jac else None)
     return r, Jpt, Jpose, Jpar
@@ -77,7 +78,7 @@ def reproj_error(model, point, pose, params, xy, want_jac=True):
 NUM_PARAMS = {0: 3, 1: 4, 2: 4, 3: 5, 4: 8, 5: 8, 6: 12, 10: 12, 11: 16, 17: 2, 7: 5, 8: 4, 9: 5, 12: 4, 13: 5, 14: 3, 15: 4, 16: 6}
 
 
-def rig_reproj_error(model, point, rig_from_world, sensor_from_rig, params, xy, want_jac=True):
+def rig_reproj_error(model, point, rig_from_world, sensor_from_rig, params, xy, want_jac=True, use=None):
     """RigReprojErrorConstantRigCostFunctor with analytic Jacobians (w.r.t. point, rig_from_world
     and the intrinsics)."""
     point = np.ascontiguousarray(point, np.float64)
@@ -90,13 +91,13 @@ def rig_reproj_error(model, point, rig_from_world, sensor_from_rig, params, xy, 
     r = np.zeros(2)
     Jpt, Jpose, Jpar = np.zeros((2, 3)), np.zeros((2, 7)), np.zeros((2, P))
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    lib().bao_rig_reproj_error(C.c_int(model), vp(point), vp(pose), vp(sens), vp(prm), vp(xy), vp(r),
+    (use or lib()).bao_rig_reproj_error(C.c_int(model), vp(point), vp(pose), vp(sens), vp(prm), vp(xy), vp(r),
                                vp(Jpt) if want_jac else None, vp(Jpose) if want_jac else None,
                                vp(Jpar) if want_jac else None)
     return r, Jpt, Jpose, Jpar
 
 
-def rig_reproj_error_sensor(model, point, rig_from_world, sensor_from_rig, params, xy):
+def rig_reproj_error_sensor(model, point, rig_from_world, sensor_from_rig, params, xy, use=None):
     """RigReprojErrorCostFunctor (variable sensor_from_rig): also the 2 x 7 Jacobian w.r.t. it."""
     point = np.ascontiguousarray(point, np.float64)
     pose = np.ascontiguousarray(rig_from_world, np.float64)
@@ -108,15 +109,15 @@ def rig_reproj_error_sensor(model, point, rig_from_world, sensor_from_rig, param
     r = np.zeros(2)
     Jpt, Jpose, Jpar, Jsens = np.zeros((2, 3)), np.zeros((2, 7)), np.zeros((2, P)), np.zeros((2, 7))
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    lib().bao_rig_reproj_error_sensor(C.c_int(model), vp(point), vp(pose), vp(sens), vp(prm), vp(xy), vp(r),
+    (use or lib()).bao_rig_reproj_error_sensor(C.c_int(model), vp(point), vp(pose), vp(sens), vp(prm), vp(xy), vp(r),
                                       vp(Jpt), vp(Jpose), vp(Jpar), vp(Jsens))
     return r, Jpt, Jpose, Jpar, Jsens
 
 
-def loss(loss_type, scale, s):
+def loss(loss_type, scale, s, use=None):
     """ceres::LossFunction::Evaluate: (rho, rho', rho'') at s = |r|^2."""
     rho = np.zeros(3)
-    lib().bao_loss(C.c_int(int(loss_type)), C.c_double(scale), C.c_double(s), rho.ctypes.data_as(C.c_void_p))
+    (use or lib()).bao_loss(C.c_int(int(loss_type)), C.c_double(scale), C.c_double(s), rho.ctypes.data_as(C.c_void_p))
     return rho
 
 
@@ -128,7 +129,7 @@ def quat_plus(q, d):
     return out
 
 
-def position_prior(position, pose, sensor=None, want_jac=True):
+def position_prior(position, pose, sensor=None, want_jac=True, use=None):
     """AbsolutePosePositionPriorCostFunctor / AbsoluteRigPosePositionPriorCostFunctor (unweighted):
     residual (3,), d/d pose (3, 7), d/d sensor_from_rig (3, 7) or None."""
     pos = np.ascontiguousarray(position, np.float64)
@@ -138,7 +139,7 @@ def position_prior(position, pose, sensor=None, want_jac=True):
     Jp = np.zeros((3, 7))
     Js = np.zeros((3, 7))
     dp = C.POINTER(C.c_double)
-    lib().bao_position_prior(pos.ctypes.data_as(dp), pose.ctypes.data_as(dp),
+    (use or lib()).bao_position_prior(pos.ctypes.data_as(dp), pose.ctypes.data_as(dp),
                              sens.ctypes.data_as(dp) if sens is not None else None, r.ctypes.data_as(dp),
                              Jp.ctypes.data_as(dp) if want_jac else None,
                              Js.ctypes.data_as(dp) if (want_jac and sens is not None) else None)

@@ -1,7 +1,8 @@
 """How two bundle-adjustment solutions of ONE problem are compared (test infrastructure).
 
-What a solve determines is compared directly: the cost (relative), the first LM iterations, the poses and the points
-(absolute). The intrinsics are compared through what they DO -- the pixel every observed point lands on, projected
+What a solve determines is compared directly: the cost (relative), the first LM iterations -- their costs and the
+trust-region radius each leaves, which the model cost change of the step decides, both under the trajectory bar -- the
+poses and the points (absolute). The intrinsics are compared through what they DO -- the pixel every observed point lands on, projected
 through either camera from the same pose and point -- not coefficient by coefficient: the reference's own test does the
 same (`ReconstructionNear`, bundle_adjustment_test.cc:344-349, compares poses and centres, never raw distortion
 coefficients), and high-order coefficients that the scene does not observe (k3 / k4 of OPENCV_FISHEYE at a narrow field
@@ -74,6 +75,7 @@ class Diff:
     sensors: float
     proj_px: float
     cams_rel: float = 0.0
+    radius_rel: float = 0.0   # trust-region radius after each of the first LM iterations (what the model cost change feeds)
 
 
     def scaled(self, f):
@@ -82,19 +84,22 @@ class Diff:
 
 # No floor, however large it measures, loosens a bar beyond this: a problem whose own perturbed solve moves further
 # than that is reported (the comparison fails) instead of passing with an arbitrary disagreement.
-CEILING = Diff(cost_rel=1e-4, traj_rel=1e-4, points=1e-2, poses=1e-2, sensors=1e-2, proj_px=1e-2, cams_rel=1e-3)
+CEILING = Diff(cost_rel=1e-4, traj_rel=1e-4, points=1e-2, poses=1e-2, sensors=1e-2, proj_px=1e-2, cams_rel=1e-3, radius_rel=1e-4)
 
 
 def diff(a, ra, b, rb, n_traj=4) -> Diff:
     n = min(n_traj, len(ra.log_cost), len(rb.log_cost))
     la, lb = np.asarray(ra.log_cost[:n], float), np.asarray(rb.log_cost[:n], float)
+    m = min(n_traj, len(ra.log_radius), len(rb.log_radius))
+    qa, qb = np.asarray(ra.log_radius[:m], float), np.asarray(rb.log_radius[:m], float)
+    rad = float((np.abs(qa - qb) / np.maximum(np.abs(qa), 1e-300)).max()) if m else 0.0
     sens = 0.0
     if a.sensors is not None and len(a.sensors):
         sens = float(np.abs(a.sensors - b.sensors).max())
     return Diff(cost_rel=abs(ra.final_cost - rb.final_cost) / max(abs(ra.final_cost), 1e-300),
                 traj_rel=float((np.abs(la - lb) / np.maximum(np.abs(la), 1e-300)).max()) if n else 0.0,
                 points=float(np.abs(a.points - b.points).max()), poses=float(np.abs(a.poses - b.poses).max()),
-                sensors=sens, proj_px=projection_diff_px(a, b), cams_rel=cams_rel_diff(a, b))
+                sensors=sens, proj_px=projection_diff_px(a, b), cams_rel=cams_rel_diff(a, b), radius_rel=rad)
 
 
 def assert_solutions_close(a, want, b, got, floor=None, cost_rtol=1e-8, param_atol=1e-6, traj_rtol=1e-7,
@@ -108,7 +113,7 @@ def assert_solutions_close(a, want, b, got, floor=None, cost_rtol=1e-8, param_at
     assert abs(got.initial_cost - want.initial_cost) <= 1e-12 * want.initial_cost
     d = diff(a, want, b, got)
     base = Diff(cost_rel=cost_rtol, traj_rel=traj_rtol, points=param_atol, poses=param_atol, sensors=param_atol,
-                proj_px=proj_atol, cams_rel=cams_rtol)
+                proj_px=proj_atol, cams_rel=cams_rtol, radius_rel=traj_rtol)
 
     def misses(bars):
         return [f"{k}: {getattr(d, k):.3e} > {getattr(bars, k):.3e}" for k in d.__dataclass_fields__

@@ -42,17 +42,30 @@ def pose_tangent_columns(pf: int) -> list:
     return cols + [3 + k for k in range(3) if k != held]
 
 
-def _correct(r, J, loss_type, scale):
+def _correct(r, J, loss_type, scale, use=None):
     """ceres::internal::Corrector on a residual block."""
     if loss_type == 0:
         return J
     s = float(r @ r)
-    rho = ba_oracle.loss(loss_type, scale, s)
+    rho = ba_oracle.loss(loss_type, scale, s, use=use)
     sqrt_rho1 = np.sqrt(rho[1])
     if s == 0.0 or rho[2] <= 0.0:
         return sqrt_rho1 * J
     alpha = 1.0 - np.sqrt(1.0 + 2.0 * s * rho[2] / rho[1])
     return sqrt_rho1 * (J - (alpha / s) * np.outer(r, r @ J))
+
+
+def _correct_residual(r, loss_type, scale, use=None):
+    """ceres::internal::Corrector::CorrectResiduals."""
+    if loss_type == 0:
+        return r
+    s = float(r @ r)
+    rho = ba_oracle.loss(loss_type, scale, s, use=use)
+    sqrt_rho1 = np.sqrt(rho[1])
+    if s == 0.0 or rho[2] <= 0.0:
+        return sqrt_rho1 * r
+    alpha = 1.0 - np.sqrt(1.0 + 2.0 * s * rho[2] / rho[1])
+    return (sqrt_rho1 / (1.0 - alpha)) * r
 
 
 class Layout:
@@ -113,10 +126,14 @@ class Layout:
         return d.get(index)
 
 
-def jacobian(fp, loss_type=0, loss_scale=1.0):
-    """Sparse tangent-space Jacobian (rows: active observations x 2, then priors x 3) and its Layout."""
+def jacobian(fp, loss_type=0, loss_scale=1.0, use=None, residuals=False):
+    """Sparse tangent-space Jacobian (rows: active observations x 2, then priors x 3) and its Layout. `use`: the checker
+    build that evaluates the observations (ba_oracle.lib() by default, ba_oracle.lib_fast() for a noise floor);
+    `residuals`: also return the loss-corrected residual vector of the same rows and, per residual block (observations,
+    then priors), the squared norm of its uncorrected residual (what the loss is evaluated at)."""
     lay = Layout(fp)
     rows, cols, vals = [], [], []
+    res, sq = [], []   # corrected residuals; squared norm of every block's uncorrected (weighted) residual
     row = 0
 
     for o in lay.active:
@@ -128,11 +145,11 @@ def jacobian(fp, loss_type=0, loss_scale=1.0):
         Js = None
         if si >= 0 and lay.sens_var[si]:
             r, Jpt, Jpose, Jpar, Js = ba_oracle.rig_reproj_error_sensor(m, fp.points[xi], fp.poses[pi], fp.sensors[si], prm,
-                                                                        fp.obs_xy[o])
+                                                                        fp.obs_xy[o], use=use)
         elif si >= 0:
-            r, Jpt, Jpose, Jpar = ba_oracle.rig_reproj_error(m, fp.points[xi], fp.poses[pi], fp.sensors[si], prm, fp.obs_xy[o])
+            r, Jpt, Jpose, Jpar = ba_oracle.rig_reproj_error(m, fp.points[xi], fp.poses[pi], fp.sensors[si], prm, fp.obs_xy[o], use=use)
         else:
-            r, Jpt, Jpose, Jpar = ba_oracle.reproj_error(m, fp.points[xi], fp.poses[pi], prm, fp.obs_xy[o])
+            r, Jpt, Jpose, Jpar = ba_oracle.reproj_error(m, fp.points[xi], fp.poses[pi], prm, fp.obs_xy[o], use=use)
         blocks = []  # (first column, 2 x k tangent Jacobian)
         if pi in lay.pose:
             off, sel = lay.pose[pi]
@@ -145,7 +162,9 @@ def jacobian(fp, loss_type=0, loss_scale=1.0):
         if xi in lay.point:
             blocks.append((lay.point[xi][0], Jpt))
         Jall = np.concatenate([b for _, b in blocks], axis=1)
-        Jall = _correct(r, Jall, loss_type, loss_scale)
+        Jall = _correct(r, Jall, loss_type, loss_scale, use)
+        res.append(_correct_residual(r, loss_type, loss_scale, use))
+        sq.append(float(r @ r))
         c0 = 0
         for off, b in blocks:
             k = b.shape[1]
@@ -161,7 +180,7 @@ def jacobian(fp, loss_type=0, loss_scale=1.0):
         si = int(fp.prior_sensor[q]) if fp.prior_sensor is not None else -1
         if pi not in lay.pose and si not in lay.sens:
             continue
-        r, Jp, Js = ba_oracle.position_prior(fp.prior_position[q], fp.poses[pi], fp.sensors[si] if si >= 0 else None)
+        r, Jp, Js = ba_oracle.position_prior(fp.prior_position[q], fp.poses[pi], fp.sensors[si] if si >= 0 else None, use=use)
         A = np.asarray(fp.prior_sqrt_info[q])
         r = A @ r
         blocks = []
@@ -170,7 +189,9 @@ def jacobian(fp, loss_type=0, loss_scale=1.0):
             blocks.append((off, (A @ Jp @ pose_manifold_jacobian(fp.poses[pi][:4]))[:, sel]))
         if si >= 0 and si in lay.sens:
             blocks.append((lay.sens[si][0], A @ Js @ pose_manifold_jacobian(fp.sensors[si][:4])))
-        Jall = _correct(r, np.concatenate([b for _, b in blocks], axis=1), int(fp.prior_loss_type), float(fp.prior_loss_scale))
+        Jall = _correct(r, np.concatenate([b for _, b in blocks], axis=1), int(fp.prior_loss_type), float(fp.prior_loss_scale), use)
+        res.append(_correct_residual(r, int(fp.prior_loss_type), float(fp.prior_loss_scale), use))
+        sq.append(float(r @ r))
         c0 = 0
         for off, b in blocks:
             k = b.shape[1]
@@ -181,6 +202,8 @@ def jacobian(fp, loss_type=0, loss_scale=1.0):
             c0 += k
         row += 3
     J = sp.csr_matrix((vals, (rows, cols)), shape=(row, lay.n))
+    if residuals:
+        return J, lay, (np.concatenate(res) if res else np.zeros(0)), np.array(sq)
     return J, lay
 
 

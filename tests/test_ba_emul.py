@@ -18,6 +18,7 @@ import subprocess
 import pytest
 
 import ba_explicit_cases as X
+import ba_step_cases as S
 import test_ba_gpu as G
 from colmap_amd import estimators as est
 
@@ -188,6 +189,45 @@ def test_tri_inverse_directly(n, j0):
 
 def test_extract_cov_blocks_directly():
     X.case_extract_cov_blocks(_host())
+
+
+# ------------------------------------------------------------------------------------------------
+# the iterative tier step by step through the probe (colmap_amd/csrc/ba_probe.h): the small cases of
+# tests/ba_step_cases.py; tests/test_ba_steps_gpu.py runs all of them on the hipcc build
+# ------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("kind,split", [("plain", True), ("narrow", False), ("kd8", True), ("kd16", True)])
+def test_steps_of_the_width_tiers(kind, split):
+    S.case_tier(_emul_lib(), kind, split)
+
+
+def test_steps_with_jacobi_scaling_and_a_robust_loss():
+    S.case_jacobi_scaling(_emul_lib())
+    S.case_loss(_emul_lib(), est.LossFunctionType.CAUCHY, 2.0)
+
+
+@pytest.mark.parametrize("model", S.OTHER_MODELS)
+def test_linearisation_of_the_other_models_against_the_checker(model):
+    S.case_model(_emul_lib(), model)
+
+
+def test_steps_of_rig_frames_and_position_priors():
+    L = _emul_lib()
+    S.case_rig(L, False)
+    S.case_rig(L, True)
+    S.case_priors(L, est.LossFunctionType.TRIVIAL)
+    S.case_priors(L, est.LossFunctionType.CAUCHY)
+
+
+def test_steps_of_pair_terms_heavy_blocks_chunk_edges_and_degenerate_problems():
+    L = _emul_lib()
+    S.case_shared_intrinsics(L, True)
+    S.case_shared_intrinsics(L, False)
+    S.case_heavy_blocks(L)
+    S.case_chunk_edges(L)
+    S.case_tiles(L, "pts")
+    S.case_degenerate(L, "points_only")
+    S.case_degenerate(L, "cameras_only")
 
 
 # ------------------------------------------------------------------------------------------------
