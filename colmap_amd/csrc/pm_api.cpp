@@ -846,15 +846,11 @@ void Create(const pm_options& opt_in, const pm_problem& prob, pm_image_cache* ca
   b.rng = h->rng.ptr;
   b.mask = nullptr;
   b.draws = nullptr;
-  {
-    // the 11 x 11 kernel reads the sweep's random numbers from a per-pixel table (one column per wave is the
-    // shape RunBatchAsync may lower to; if that fits the workgroup's LDS budget the table is needed)
-    PmParams probe = b;
-    probe.C = 1;
-    if (pm_sweep_uses_draws(probe, opt.geom_consistency != 0)) {
-      h->draws.alloc((size_t)W * H * pm_draw_stride(b.num_samples));
-      b.draws = h->draws.ptr;
-    }
+  // the 11 x 11 kernels read the sweep's random numbers from a per-pixel table (one column per wave is the
+  // shape RunBatchAsync may lower to; if that fits the workgroup's LDS budget the table is needed)
+  if (PmRunPlan::wave_kernels_fit(b, 1, opt.geom_consistency != 0)) {
+    h->draws.alloc((size_t)W * H * pm_draw_stride(b.num_samples));
+    b.draws = h->draws.ptr;
   }
 
   PmParams p0 = ParamsForSweep(h, 0);
@@ -925,12 +921,20 @@ void RunBatchAsync(pm_handle** hs, int n, hipStream_t run_st = nullptr) {
   // One launch geometry for the batch: the columns per wave of THIS run are a property of the run (every parameter
   // block of the run carries it), never written back to a handle -- a handle re-run in another batch, or traced, sees
   // its own shape again.
-  int run_C = h0->base.C, run_help = 1;
-  for (int b = 1; b < n; ++b) run_C = std::min(run_C, hs[b]->base.C);
+  const bool geom = opt.geom_consistency != 0;
+  int run_C = 64, run_help = 1;  // (64: pm_pick_columns never gives more)
   {
+    // COLMAP_AMD_PM_COLS (experiments): columns per group for the handles that requested none
+    const int cols_switch = dev_switch_int("COLMAP_AMD_PM_COLS", 0);
     bool automatic = h0->base.ntaps == 121;
-    for (int b = 0; b < n; ++b) automatic = automatic && hs[b]->opt.columns_per_group <= 0;
-    if (automatic && dev_switch_int("COLMAP_AMD_PM_COLS", 0) <= 0) {
+    for (int b = 0; b < n; ++b) {
+      const PmParams& s = hs[b]->base;
+      const bool requested = hs[b]->opt.columns_per_group > 0;
+      run_C = std::min(run_C, !requested && cols_switch > 0
+                                  ? pm_pick_columns(s.S, s.ntaps, s.num_samples, geom, s.radius, cols_switch) : s.C);
+      automatic = automatic && !requested;
+    }
+    if (automatic && cols_switch <= 0) {
       static std::atomic<int> cus[16];
       int ncu = cus[h0->device & 15].load();
       if (ncu == 0) {
@@ -972,9 +976,14 @@ void RunBatchAsync(pm_handle** hs, int n, hipStream_t run_st = nullptr) {
   const int xcd_map_env = dev_switch_int("COLMAP_AMD_PM_XCD_MAP", 0);
   const int xcd_map = (xcd_map_env == 1 && n % 8 == 0) ? 1 : (xcd_map_env == 2 ? 2 : 0);
   int sel_out = h0->base.sel_out_off, sel_in = h0->base.sel_in_off;
-  // one kernel serves the whole batch: buffer-resource addressing only if every problem's images allow it
-  bool fp_resource_all = true;
-  for (int b = 0; b < n; ++b) fp_resource_all = fp_resource_all && hs[b]->fp_base != nullptr;
+  // Which kernels the run launches, decided once. One kernel serves the whole batch: buffer-resource addressing only if
+  // every problem's images allow it -- otherwise NO parameter block of the run carries a base.
+  bool fp_base_all = true;
+  for (int b = 0; b < n; ++b) fp_base_all = fp_base_all && hs[b]->fp_base != nullptr;
+  const PmRunPlan run_plan = pm_plan_run(host[0], geom, h0->threads, fp_base_all, h0->base.prof != nullptr,
+                                         h0->base.draws != nullptr);
+  if (!run_plan.fp_resource)
+    for (int b = 0; b < n; ++b) host[b].fp_base = nullptr;
   for (int k = 0; k < limit; ++k) {
     const int iter = k / 4, sweep = k % 4;
     for (int b = 0; b < n; ++b) {
@@ -1000,7 +1009,7 @@ void RunBatchAsync(pm_handle** hs, int n, hipStream_t run_st = nullptr) {
 #else
       p.ablate = 0;
 #endif
-      if (!fp_resource_all) p.fp_base = nullptr;
+      if (!run_plan.fp_resource) p.fp_base = nullptr;
       host[(size_t)(k + 1) * n + b] = p;
     }
     std::swap(sel_out, sel_in);  // Rotate(): prev_sel_prob <- sel_prob (reference :1911-1915)
@@ -1019,8 +1028,7 @@ void RunBatchAsync(pm_handle** hs, int n, hipStream_t run_st = nullptr) {
       HIP_CALL(hipMemsetAsync(h->prof.ptr, 0, kPmProfSlots * sizeof(unsigned long long), st));
     HIP_CALL(hipMemsetAsync(h->evals.ptr, 0, sizeof(unsigned long long), st));
   }
-  pm_launch_initial_cost(host[0], h0->plan.ptr, n, st);
-  const bool geom = opt.geom_consistency != 0;
+  pm_launch_initial_cost(run_plan, h0->plan.ptr, n, st);
   for (int k = 0; k < limit; ++k) {
     const bool last_sweep = k == total_sweeps - 1;
     const bool fphoto = last_sweep && opt.filter;
@@ -1028,10 +1036,10 @@ void RunBatchAsync(pm_handle** hs, int n, hipStream_t run_st = nullptr) {
     for (int b = 0; b < n; ++b)  // debug progress trace: every launch starts from an empty buffer
       if (hs[b]->trace.ptr)
         HIP_CALL(hipMemsetAsync(hs[b]->trace.ptr, 0, hs[b]->trace.count * sizeof(unsigned long long), st));
-    pm_launch_draws(host[(size_t)(k + 1) * n], h0->plan.ptr + (size_t)(k + 1) * n, n, geom, st);
+    pm_launch_draws(run_plan, k % 4, h0->plan.ptr + (size_t)(k + 1) * n, n, st);
     HIP_CALL(hipEventRecord(h0->ev[2 * k], st));   // the events bracket the sweep kernel alone
-    h0->sweep_kernel = pm_launch_sweep(host[(size_t)(k + 1) * n], h0->plan.ptr + (size_t)(k + 1) * n, n,
-                                       h0->threads, geom, fphoto, fgeom, st);
+    pm_launch_sweep(run_plan, k % 4, h0->plan.ptr + (size_t)(k + 1) * n, n, fphoto, fgeom, st);
+    h0->sweep_kernel = run_plan.sweep_name;
     HIP_CALL(hipEventRecord(h0->ev[2 * k + 1], st));
   }
   for (int b = 0; b < n; ++b) {

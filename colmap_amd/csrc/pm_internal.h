@@ -16,7 +16,7 @@ namespace colmap_amd {
 
 constexpr int kPoseStride = 43;  // K4 R9 T3 C3 P12 invP12 (reference patch_match_cuda.cu:1762)
 constexpr int kRngWords = 6;     // XORWOW: x[5] + d
-constexpr int kPmProfSlots = 24; // phase-profile counters per handle (pm_kernels.hip: kProf*; the generic kernel uses 10)
+constexpr int kPmProfSlots = 24; // phase-profile counters per handle (pm_kernels.hip: kProf*, written by pm_sweep_quad_prof_kernel only)
 
 // Packed source images ("footprints": one dword per texel position = its 2 x 2 bilinear neighbourhood) are
 // stored as vertical strips of kFpStrip = 16 entries: inside a strip the rows follow each other, 64 bytes each, so
@@ -97,10 +97,34 @@ struct PmParams {
 
 // floats per pixel of PmParams::draws: perturbed depth, perturbed normal, M uniforms (whole float4s)
 __host__ __device__ inline int pm_draw_stride(int M) { return 4 + ((M + 3) & ~3); }
-// does the sweep of this shape run the 11 x 11 kernel that reads PmParams::draws?
-bool pm_sweep_uses_draws(const PmParams& p, bool geom);
-size_t pm_sweep_lds_bytes(const PmParams& p, bool geom);
+// `requested` > 0: the caller's columns per group (PatchMatchOptions::columns_per_group or the development switch)
 int pm_pick_columns(int S, int ntaps, int num_samples, bool geom, int radius, int requested);
+
+// Which kernels a run launches, decided ONCE per run (pm_plan_run) from the common shape of its problems; the launchers
+// below only launch what the plan states. Two families, one arithmetic: the 11 x 11 wave kernels (quad; pair = a helper
+// wave per column group; quad-prof = the quad kernel with its phase clocks) and the generic kernel of any window.
+enum PmFamily { kPmGeneric, kPmQuad, kPmPair, kPmQuadProf };
+struct PmRunPlan {
+  PmFamily initial_cost;    // kPmGeneric or kPmQuad
+  PmFamily sweep;
+  bool fp_resource;         // wave kernels: packed images through the problem's buffer resource (else explicit indices).
+                            // One flag for the initial cost and every sweep; false = every parameter block of the run
+                            // carries fp_base = null (RunBatchAsync)
+  bool geom;
+  int W, H, C;              // grid geometry: un-rotated image size, columns per group
+  int initial_cost_block, sweep_block;     // threads per workgroup
+  size_t initial_cost_lds, sweep_lds;      // dynamic LDS bytes
+  const char* sweep_name;   // what pm_get_sweep_kernel_name reports
+
+  // The one shape test of the plan: do the 11 x 11 wave kernels serve this shape (window, source count and the
+  // four-wave workgroup's LDS budget at C columns per wave)? They read the sweep's random numbers from PmParams::draws:
+  // pm_create asks with C = 1, the narrowest shape a run may choose, whether to allocate them.
+  static bool wave_kernels_fit(const PmParams& shape, int C, bool geom);
+};
+// `shape`: the parameter block of any problem of the run, with the run's C and help; `threads`: workgroup size of the
+// generic sweep kernel; fp_base_all: every handle of the batch has a buffer-resource base; draws: PmParams::draws is
+// allocated. The only reader of COLMAP_AMD_PM_WAVE and COLMAP_AMD_PM_FP_GLOBAL.
+PmRunPlan pm_plan_run(const PmParams& shape, bool geom, int threads, bool fp_base_all, bool profile, bool draws);
 
 void pm_launch_build_footprint(const uint8_t* src, uint32_t* fp, int S, int w, int h, hipStream_t st);
 void pm_launch_filter_ref(const uint8_t* gray, int W, int H, int radius, int step, float sigma_spatial,
@@ -108,15 +132,13 @@ void pm_launch_filter_ref(const uint8_t* gray, int W, int H, int radius, int ste
                           hipStream_t st);
 void pm_launch_init_state(const PmParams& p, bool random_init, float depth_min, float depth_max,
                           const float* init_depth, const float* init_normal, hipStream_t st);
-// `p` describes the (identical) shape of every problem of the batch; `dev_params` is the
-// device array of per-problem parameter blocks the kernel indexes with its batch coordinate.
-void pm_launch_initial_cost(const PmParams& p, const PmParams* dev_params, int batch, hipStream_t st);
-// the random numbers of the next sweep launch (11 x 11 kernel; no-op for shapes the generic kernel serves): call before
-// pm_launch_sweep with the same arguments
-void pm_launch_draws(const PmParams& p, const PmParams* dev_params, int batch, bool geom, hipStream_t st);
-// returns the name of the kernel it launched
-const char* pm_launch_sweep(const PmParams& p, const PmParams* dev_params, int batch, int threads, bool geom,
-                            bool filter_photo, bool filter_geom, hipStream_t st);
+// `dev_params` is the device array of per-problem parameter blocks the kernel indexes with its batch coordinate.
+void pm_launch_initial_cost(const PmRunPlan& plan, const PmParams* dev_params, int batch, hipStream_t st);
+// the random numbers of the next sweep launch (wave kernels; no-op when the generic kernel sweeps, it draws in place):
+// call before pm_launch_sweep with the same arguments; `rot` = the sweep's direction (PmParams::rot)
+void pm_launch_draws(const PmRunPlan& plan, int rot, const PmParams* dev_params, int batch, hipStream_t st);
+void pm_launch_sweep(const PmRunPlan& plan, int rot, const PmParams* dev_params, int batch, bool filter_photo,
+                     bool filter_geom, hipStream_t st);
 void pm_launch_rng_streams(const unsigned long long* seeds, int nseeds, int ndraws, float* out,
                            hipStream_t st);
 void pm_launch_extract(const PmParams& p, int sel_off, float* depth, float* normal, float* sel,

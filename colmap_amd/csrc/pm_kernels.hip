@@ -38,6 +38,8 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 namespace colmap_amd {
 
 // ---------------------------------------------------------------------------
@@ -284,13 +286,9 @@ __device__ __forceinline__ float reduce16(float v) {
 __host__ __device__ inline int tap_stride(int ntaps) { return ((ntaps + 127) / 128) * 128; }
 
 // Per-tap bilateral weights and reference colours of one lane (taps j + 16 k, k = 0..7) held in
-// registers across consecutive evaluations of the same pixel column (fixed window <= 128 taps).
+// registers across consecutive evaluations of the same pixel column (11 x 11 wave kernels: ncc_back).
 struct TapRegs {
   v2f w[4], r[4];
-};
-template <int N1D>
-struct TapRegsUsed {
-  static constexpr bool value = N1D > 0 && N1D * N1D <= 128;
 };
 __device__ __forceinline__ void tap_regs_load(TapRegs& R, const lds_f32* wgt, const lds_f32* refc, int j) {
   const lds_f32* wj = wgt + j;
@@ -318,13 +316,12 @@ __device__ __forceinline__ void tap_regs_load(TapRegs& R, const lds_f32* wgt, co
 // division -- inv_k = (prod_{i<k} z_i * prod_{i>k} z_i) / prod z_i, prefix products taken in
 // increasing k and the suffix product in decreasing k; taps beyond the window use z = 1, weight 0;
 // even-k and odd-k taps accumulate separately and are added before the cross-lane tree.
-template <int N1D>
 __device__ __forceinline__ void ncc_group(const PmParams& p, const lds_f32* H, gbl_u32* fp,
-                                          const lds_f32* wgt, const lds_f32* refc, const TapRegs& R,
+                                          const lds_f32* wgt, const lds_f32* refc,
                                           int j, float& s_sum, float& s_sq, float& s_ref) {
   const float h0 = H[0], h1 = H[1], h2 = H[2], h3 = H[3], h4 = H[4], h5 = H[5], h6 = H[6],
               h7 = H[7], h8 = H[8];
-  const int n1d = N1D > 0 ? N1D : p.ntap1d;
+  const int n1d = p.ntap1d;
   const int ntaps = n1d * n1d;
   const lds_f32* wj = wgt + j;
   const lds_f32* rj = refc + j;
@@ -406,29 +403,18 @@ __device__ __forceinline__ void ncc_group(const PmParams& p, const lds_f32* H, g
       const v2f src = pk_fma(wy[q], bot - top, top) * pk_bcast(0x1.010102p-8f);
       const int t0 = 16 * (kb + 2 * q);  // one base register + immediate offsets: ds_read2_b32
       v2f w2, r2;
-      if (TapRegsUsed<N1D>::value) {
-        w2 = R.w[q];
-        r2 = R.r[q];
-      } else {
-        w2[0] = wj[t0];
-        w2[1] = wj[t0 + 16];
-        r2[0] = rj[t0];
-        r2[1] = rj[t0 + 16];
-      }
+      w2[0] = wj[t0];
+      w2[1] = wj[t0 + 16];
+      r2[0] = rj[t0];
+      r2[1] = rj[t0 + 16];
       const v2f bws = w2 * src;
       a_sum = a_sum + bws;
       a_sq = pk_fma(bws, src, a_sq);
       a_ref = pk_fma(bws, r2, a_ref);
     }
   };
-  if (N1D > 0) {
-    constexpr int NCHUNK = (N1D * N1D + 127) / 128 > 0 ? (N1D * N1D + 127) / 128 : 1;
-#pragma unroll
-    for (int c = 0; c < NCHUNK; ++c) chunk(8 * c);
-  } else {
-    const int nchunk = (ntaps + 127) / 128;
-    for (int c = 0; c < nchunk; ++c) chunk(8 * c);
-  }
+  const int nchunk = (ntaps + 127) / 128;
+  for (int c = 0; c < nchunk; ++c) chunk(8 * c);
   // The three window sums (not yet normalised); ncc_finish() turns them into the cost. The callers
   // park them in LDS and finish all evaluations of a phase lane-per-evaluation: square root and
   // division are then paid once per evaluation instead of once per lane of its group.
@@ -930,7 +916,6 @@ __device__ __forceinline__ void patch_weight_sums(const PmParams& p, const Lds& 
 // ComputeInitialCost (patch_match_cuda.cu:863-912): C adjacent pixels of one row
 // per workgroup, C*S NCC evaluations spread over the lanes. Rotation 0.
 // ---------------------------------------------------------------------------
-template <int N1D>
 __global__ void __launch_bounds__(64) pm_initial_cost_kernel(const PmParams* __restrict__ pp) {
   const PmParams& p = pp[blockIdx.z];  // batch of reference images: one launch, grid.z problems
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -960,20 +945,14 @@ __global__ void __launch_bounds__(64) pm_initial_cost_kernel(const PmParams* __r
   __syncthreads();
   // NCC: 16-lane group per task
   const int g = tid >> 4, j = tid & 15, ng = nt >> 4;
-  TapRegs R;
-  int c_held = -1;
   for (int item = g; item < p.C * p.S; item += ng) {
     const int c = item / p.S;
     const int s = item - c * p.S;
     const int col = col0 + c;
     if (col >= p.W) continue;
-    if (TapRegsUsed<N1D>::value && c != c_held) {
-      tap_regs_load(R, L.wgt + c * tap_stride(p.ntaps), L.refc + c * tap_stride(p.ntaps), j);
-      c_held = c;
-    }
     float s_sum, s_sq, s_ref;
-    ncc_group<N1D>(p, L.th + item * 9, (gbl_u32*)L.fpb[s], L.wgt + c * tap_stride(p.ntaps),
-                   L.refc + c * tap_stride(p.ntaps), R, j, s_sum, s_sq, s_ref);
+    ncc_group(p, L.th + item * 9, (gbl_u32*)L.fpb[s], L.wgt + c * tap_stride(p.ntaps),
+              L.refc + c * tap_stride(p.ntaps), j, s_sum, s_sq, s_ref);
     if (j == 0) {
       L.th[item * 9 + 0] = s_sum;  // the homography of this evaluation is no longer needed
       L.th[item * 9 + 1] = s_sq;
@@ -1000,7 +979,7 @@ __global__ void __launch_bounds__(64) pm_initial_cost_kernel(const PmParams* __r
 // Run every queued NCC / geometric-cost task. Pass A (lane per task): homography of
 // the (hypothesis, view) pair and, with GEOM, the geometric consistency cost. Pass B
 // (16-lane group per task): the bilaterally weighted NCC.
-template <int N1D, bool GEOM>
+template <bool GEOM>
 __device__ __forceinline__ int run_tasks(const PmParams& p, const Lds& L, int row, int col0,
                                          int tid, int nt) {
   const int n = *L.ntasks;
@@ -1025,23 +1004,14 @@ __device__ __forceinline__ int run_tasks(const PmParams& p, const Lds& L, int ro
   }
   __syncthreads();
   const int g = tid >> 4, j = tid & 15, ng = nt >> 4;
-  // A wave's four groups work on the four hypotheses of one (column, view) block, and the blocks
-  // of a column are mostly adjacent in the list: the column's tap weights stay in registers
-  // until the column changes.
-  TapRegs R;
-  int c_held = -1;
   for (int t = g; t < n; t += ng) {
     const uint32_t task = L.tasks[t];
     if ((task >> 23) & 1) continue;  // geometric cost only
     const int c = task >> 24;
     const int s = task & 0xfffff;
-    if (TapRegsUsed<N1D>::value && c != c_held) {
-      tap_regs_load(R, L.wgt + c * tap_stride(p.ntaps), L.refc + c * tap_stride(p.ntaps), j);
-      c_held = c;
-    }
     float s_sum, s_sq, s_ref;
-    ncc_group<N1D>(p, L.th + t * 9, (gbl_u32*)L.fpb[s], L.wgt + c * tap_stride(p.ntaps),
-                   L.refc + c * tap_stride(p.ntaps), R, j, s_sum, s_sq, s_ref);
+    ncc_group(p, L.th + t * 9, (gbl_u32*)L.fpb[s], L.wgt + c * tap_stride(p.ntaps),
+              L.refc + c * tap_stride(p.ntaps), j, s_sum, s_sq, s_ref);
     if (j == 0) {
       L.th[t * 9 + 0] = s_sum;  // the homography of this task is no longer needed
       L.th[t * 9 + 1] = s_sq;
@@ -1087,7 +1057,7 @@ struct NccStage {  // what the back half needs from the front half besides the t
 
 __device__ __forceinline__ v4i fp_resource(const PmParams& p) {
   const uint64_t b = (uint64_t)p.fp_base;
-  const uint32_t stride = 4u * ((uint32_t)p.fp_rows1 + 1u);  // bytes; < 16384 (pm_fp_resource_ok)
+  const uint32_t stride = 4u * ((uint32_t)p.fp_rows1 + 1u);  // bytes; < 16384 (pm_plan_run: fp_resource)
   v4i r;
   r[0] = (int)(uint32_t)b;
   r[1] = (int)(((uint32_t)(b >> 32) & 0xffffu) | (stride << 16) | 0x80000000u);  // swizzle enable
@@ -1215,8 +1185,8 @@ __device__ __forceinline__ void ncc_back(const NccStage& st, const uint32_t tex[
   reduce16x3(s_sum, s_sq, s_ref);
 }
 
-// Optional phase profile: PROF instantiation only; wave 0 / lane 0 accumulates
-// shader-clock deltas per phase and adds them to p.prof[] at the end.
+// Phase profile of the 11 x 11 wave kernels (sweep_wave_body / run_tasks_wave, PROF instantiation only: kProf*
+// below); the generic kernel has none.
 #define PM_PROF_MARK(slot)                                   \
   if (PROF) {                                                \
     const unsigned long long now_ = __builtin_readcyclecounter(); \
@@ -1232,7 +1202,7 @@ __device__ __forceinline__ void ncc_back(const NccStage& st, const uint32_t tex[
 #define PM_MARK(name)
 #endif
 
-template <int N1D, bool GEOM, bool FILTER_PHOTO, bool FILTER_GEOM, bool PROF>
+template <bool GEOM, bool FILTER_PHOTO, bool FILTER_GEOM>
 __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __restrict__ pp) {
   // Batch of reference images: one launch, grid.y problems. Workgroups are dealt to the 8 XCDs
   // round-robin by linear id, so problem = id % batch keeps each problem's source-image band in
@@ -1257,9 +1227,6 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
   const int col0 = group * C;
   const int ncols = min(C, RW - col0);  // valid columns of this group
   const float* iK = p.refInvK;
-
-  unsigned long long prof_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long prof_t = PROF ? __builtin_readcyclecounter() : 0ull;
 
   lds_load_poses(p, L, GEOM, tid, nt);
 
@@ -1292,7 +1259,6 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
   // reference tile rows [-r, r-1]; row r arrives in the first loop iteration
   for (int r = -p.radius; r < p.radius; ++r) tile_load_row(p, L, col0, r, tid, nt);
   __syncthreads();
-  PM_PROF_MARK(0)
 
   unsigned evals2 = 0;
   for (int row = 0; row < RH; ++row) {
@@ -1300,7 +1266,6 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
     tile_load_row(p, L, col0, row + p.radius, tid, nt);
     if (tid == 0) *L.ntasks = 0;
     __syncthreads();
-    PM_PROF_MARK(1)
 
     // ---- P1: hypotheses (lane per column) + patch weights (all lanes) --------
     if (col_lane) {
@@ -1338,7 +1303,6 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
     patch_weights(p, L, row, tid, nt);
     for (int item = tid; item < ncols * 5 * S; item += nt) L.ncc[item] = -1.0f;
     __syncthreads();
-    PM_PROF_MARK(2)
 
     // ---- P2: per-view selection priors (:1070-1104), lane per (column, view) --
     patch_weight_sums(p, L, ncols, tid, nt);
@@ -1368,7 +1332,6 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
       L.q[item] = sp * tp * ip * rp;
     }
     __syncthreads();
-    PM_PROF_MARK(3)
 
     // ---- P3a: TransformPDFToCDF (:683-696), sequential sum order, lane per column
     if (col_lane) {
@@ -1412,14 +1375,12 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
       }
     }
     __syncthreads();
-    PM_PROF_MARK(4)
 
     // ---- P4: NCC of hypotheses 1..4 against the drawn views (:1157-1172) -----
-    evals2 += (unsigned)run_tasks<N1D, GEOM>(p, L, row, col0, tid, nt);
+    evals2 += (unsigned)run_tasks<GEOM>(p, L, row, col0, tid, nt);
     __syncthreads();
     if (tid == 0) *L.ntasks = 0;
     __syncthreads();
-    PM_PROF_MARK(5)
 
     // ---- P5a: accumulate in draw order (:1144-1172), lane per (column, hypothesis)
     for (int item = tid; item < ncols * 5; item += nt) {
@@ -1467,12 +1428,10 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
       }
     }
     __syncthreads();
-    PM_PROF_MARK(6)
 
     // ---- P6: NCC of the winner against the remaining views (:1188-1197) ------
-    evals2 += (unsigned)run_tasks<N1D, false>(p, L, row, col0, tid, nt);
+    evals2 += (unsigned)run_tasks<false>(p, L, row, col0, tid, nt);
     __syncthreads();
-    PM_PROF_MARK(7)
 
     // ---- P7: cost map, forward message, selection probability (:1186-1207) ---
     for (int item = tid; item < ncols * S; item += nt) {
@@ -1531,16 +1490,12 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
       }
     }
     __syncthreads();
-    PM_PROF_MARK(8)
   }
 
   if (col_lane) {
     rng_store(p.rng + (size_t)pix_index(p, 0, col0 + tid) * kRngWords, rng);  // :1285-1287
   }
   if (tid == 0 && p.evals) atomicAdd(p.evals, (unsigned long long)evals2);
-  if (PROF && tid == 0 && p.prof) {
-    for (int i = 0; i < 10; ++i) atomicAdd(p.prof + i, prof_acc[i]);
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -2519,27 +2474,21 @@ __global__ void __launch_bounds__(256) pm_extract_kernel(const PmParams p, int s
 // Launchers
 // ---------------------------------------------------------------------------
 
-size_t pm_sweep_lds_bytes(const PmParams& p, bool geom) {
-  return lds_offsets(p.C, p.S, p.radius, p.ntaps, p.num_samples, geom).total;
-}
-
 // LDS budget of one four-wave workgroup when four of them share a CU: 160 KB / 4 in 1280-byte granules.
 constexpr size_t kQuadLdsBudget = 40960;
 
-// Is this shape served by the 11 x 11 four-wave kernel (else: the generic kernel)?
-static bool pm_wave_shape(int ntap1d, int step, int S, int C) { return ntap1d == 11 && step >= 1 && S <= 512 && C <= 8; }
+static size_t wave_lds_bytes(const PmParams& p, int C, bool geom, int nw) {
+  return lds_offsets_wave(C, p.S, p.radius, p.ntaps, p.num_samples, geom, kQuadThCap, nw).total;
+}
 
-bool pm_sweep_uses_draws(const PmParams& p, bool geom) {
-  return pm_wave_shape(p.ntap1d, p.step, p.S, p.C) &&
-         lds_offsets_wave(p.C, p.S, p.radius, p.ntaps, p.num_samples, geom, kQuadThCap, kQuadWaves).total <= kQuadLdsBudget;
+bool PmRunPlan::wave_kernels_fit(const PmParams& p, int C, bool geom) {
+  return p.ntap1d == 11 && p.step >= 1 && p.S <= 512 && C <= 8 && wave_lds_bytes(p, C, geom, kQuadWaves) <= kQuadLdsBudget;
 }
 
 int pm_pick_columns(int S, int ntaps, int num_samples, bool geom, int radius, int requested) {
   const size_t budget = 60 * 1024;
   // default: 2 columns per wave of the 11 x 11 kernel (16 waves resident per CU, the lane-per-(column, view)
   // phases are one pass; measured 604 / 643 / 718 ms per 16-image launch for C = 2 / 3 / 4), 4 for the generic kernel
-  const int cols_env = dev_switch_int("COLMAP_AMD_PM_COLS", 0);  // experiments / tests
-  if (requested <= 0 && cols_env > 0) requested = cols_env;
   int c = requested > 0 ? requested : (ntaps == 121 ? 2 : 4);
   if (c > 64) c = 64;
   if (ntaps == 121 && requested <= 0) {
@@ -2550,11 +2499,56 @@ int pm_pick_columns(int S, int ntaps, int num_samples, bool geom, int radius, in
   return c;
 }
 
-// Can the 11 x 11 sweep kernels address this problem's packed source images through one buffer resource
-// (fp_resource)? The host has found all images inside a 4 GB window (pm_api.cpp) and the stride field of the
-// resource holds 4 * rows < 2^14.
-static bool pm_fp_resource_ok(const PmParams& p) {
-  return p.fp_base != nullptr && p.src_fp_off != nullptr && 4 * (p.fp_rows1 + 1) < (1 << 14);
+// Which kernels serve a run (two families, both produce the same bits):
+//  * the 11 x 11 wave kernels -- four-wave workgroups whose waves each sweep their own column group
+//    (pm_sweep_quad_kernel), fed by pm_draw_kernel (the sweep's random numbers), and the sweep-shaped
+//    pm_initial_cost_wave_kernel: whenever the shape fits (wave_kernels_fit). They exist with and without the
+//    buffer-resource addressing of the packed images (fp_resource); with it also as pm_sweep_pair_kernel (help = 2 at one
+//    column per wave) and, photometric sweeps, as pm_sweep_quad_prof_kernel (phase profile enabled);
+//  * pm_sweep_kernel / pm_initial_cost_kernel -- any window, workgroups with barriers (round 1's design), no phase
+//    profile: other window sizes, more source images than the four-wave LDS block holds, more than 8 columns per
+//    group, COLMAP_AMD_PM_WAVE=0 (tests: the A/B reference at the 11 x 11 window).
+PmRunPlan pm_plan_run(const PmParams& p, bool geom, int threads, bool fp_base_all, bool profile, bool draws) {
+  PmRunPlan plan;
+  plan.geom = geom;
+  plan.W = p.W; plan.H = p.H; plan.C = p.C;
+  const bool wave = dev_switch_int("COLMAP_AMD_PM_WAVE", 1) != 0;
+  // One buffer resource per problem (fp_resource): the host has found all its images inside a 4 GB window
+  // (pm_api.cpp) and the stride field of the resource holds 4 * rows < 2^14. One kernel serves the whole batch, so
+  // every problem must allow it. COLMAP_AMD_PM_FP_GLOBAL=1 (tests): explicit indices although the resource would do.
+  plan.fp_resource = fp_base_all && p.src_fp_off != nullptr && 4 * (p.fp_rows1 + 1) < (1 << 14) &&
+                     dev_switch_int("COLMAP_AMD_PM_FP_GLOBAL", 0) == 0;
+  // the initial cost is photometric and needs no draws
+  plan.initial_cost = wave && PmRunPlan::wave_kernels_fit(p, p.C, false) ? kPmQuad : kPmGeneric;
+  if (plan.initial_cost == kPmQuad) {
+    plan.initial_cost_block = 64 * kQuadWaves;
+    plan.initial_cost_lds = wave_lds_bytes(p, p.C, false, kQuadWaves);
+  } else {
+    plan.initial_cost_block = 64;
+    plan.initial_cost_lds = lds_offsets(p.C, p.S, p.radius, p.ntaps, p.num_samples, false).total;
+  }
+  if (!(wave && draws && PmRunPlan::wave_kernels_fit(p, p.C, geom))) {
+    plan.sweep = kPmGeneric;
+    plan.sweep_name = "pm_sweep_kernel";
+    plan.sweep_block = threads;
+    plan.sweep_lds = lds_offsets(p.C, p.S, p.radius, p.ntaps, p.num_samples, geom).total;
+  } else {
+    plan.sweep_block = 64 * kQuadWaves;
+    plan.sweep_lds = wave_lds_bytes(p, p.C, geom, kQuadWaves);
+    if (profile && plan.fp_resource && !geom) {
+      plan.sweep = kPmQuadProf;  // the shipped kernel with its phase clocks compiled in (photometric sweeps)
+      plan.sweep_name = "pm_sweep_quad_prof_kernel";
+    } else if (p.help > 1 && plan.fp_resource && p.C == 1) {
+      plan.sweep = kPmPair;      // two waves per column group, one group per workgroup
+      plan.sweep_name = "pm_sweep_pair_kernel";
+      plan.sweep_block = 128;
+      plan.sweep_lds = wave_lds_bytes(p, p.C, geom, 1);
+    } else {
+      plan.sweep = kPmQuad;
+      plan.sweep_name = plan.fp_resource ? "pm_sweep_quad_kernel" : "pm_sweep_quad_kernel (explicit indices)";
+    }
+  }
+  return plan;
 }
 
 void pm_launch_build_footprint(const uint8_t* src, uint32_t* fp, int S, int w, int h, hipStream_t st) {
@@ -2583,98 +2577,67 @@ void pm_launch_init_state(const PmParams& p, bool random_init, float depth_min, 
                      depth_max, init_depth, init_normal);
 }
 
-void pm_launch_initial_cost(const PmParams& p, const PmParams* dev_params, int batch, hipStream_t st) {
-  // 11 x 11 window and a shape the four-wave LDS block holds: the sweep-shaped kernel (COLMAP_AMD_PM_WAVE=0: tests)
-  if (dev_switch_int("COLMAP_AMD_PM_WAVE", 1) != 0 && pm_sweep_uses_draws(p, false)) {
-    const bool mubuf = pm_fp_resource_ok(p) && dev_switch_int("COLMAP_AMD_PM_FP_GLOBAL", 0) == 0;
-    const size_t qlds = lds_offsets_wave(p.C, p.S, p.radius, p.ntaps, p.num_samples, false, kQuadThCap, kQuadWaves).total;
-    const unsigned groups = (unsigned)((p.W + p.C - 1) / p.C);
-    const dim3 grid((groups + kQuadWaves - 1) / kQuadWaves, (unsigned)((p.H + kInitRows - 1) / kInitRows), batch);
-    if (mubuf) hipLaunchKernelGGL(pm_initial_cost_wave_kernel<true>, grid, dim3(64 * kQuadWaves), qlds, st, dev_params);
-    else hipLaunchKernelGGL(pm_initial_cost_wave_kernel<false>, grid, dim3(64 * kQuadWaves), qlds, st, dev_params);
-    return;
+void pm_launch_initial_cost(const PmRunPlan& plan, const PmParams* dev_params, int batch, hipStream_t st) {
+  const unsigned groups = (unsigned)((plan.W + plan.C - 1) / plan.C);
+  const dim3 block(plan.initial_cost_block, 1, 1);
+  if (plan.initial_cost == kPmQuad) {
+    const dim3 grid((groups + kQuadWaves - 1) / kQuadWaves, (unsigned)((plan.H + kInitRows - 1) / kInitRows), batch);
+    if (plan.fp_resource) hipLaunchKernelGGL(pm_initial_cost_wave_kernel<true>, grid, block, plan.initial_cost_lds, st, dev_params);
+    else hipLaunchKernelGGL(pm_initial_cost_wave_kernel<false>, grid, block, plan.initial_cost_lds, st, dev_params);
+  } else {
+    hipLaunchKernelGGL(pm_initial_cost_kernel, dim3(groups, plan.H, batch), block, plan.initial_cost_lds, st, dev_params);
   }
-  const size_t lds = lds_offsets(p.C, p.S, p.radius, p.ntaps, p.num_samples, false).total;
-  dim3 block(64, 1, 1);
-  dim3 grid((p.W + p.C - 1) / p.C, p.H, batch);
-  if (p.ntap1d == 11) hipLaunchKernelGGL(pm_initial_cost_kernel<11>, grid, block, lds, st, dev_params);
-  else hipLaunchKernelGGL(pm_initial_cost_kernel<0>, grid, block, lds, st, dev_params);
 }
 
-// Which sweep kernel runs (two families):
-//  * pm_sweep_quad_kernel -- 11 x 11 window, four-wave workgroups whose waves each sweep their own column group, fed
-//    by pm_draw_kernel (the sweep's random numbers): whenever four workgroups fit a CU;
-//  * pm_sweep_kernel      -- any window, 256-thread workgroups with barriers (round 1's design): other window
-//    sizes, more source images than the four-wave LDS block holds, COLMAP_AMD_PM_WAVE=0.
-// The 11 x 11 kernel exists with and without the buffer-resource addressing of the packed images (fp_resource).
-// Both families produce the same bits.
 // The sweep's random numbers (pm_draw_kernel), launched in front of a sweep that reads them; a launch of its own so
 // that the caller's events bracket the sweep kernel alone.
-static bool pm_sweep_takes_wave_kernel(const PmParams& p, bool geom) {
-  return dev_switch_int("COLMAP_AMD_PM_WAVE", 1) != 0 && p.draws != nullptr && pm_sweep_uses_draws(p, geom);
-}
-void pm_launch_draws(const PmParams& p, const PmParams* dev_params, int batch, bool geom, hipStream_t st) {
-  if (!pm_sweep_takes_wave_kernel(p, geom)) return;
-  const int rw = (p.rot & 1) ? p.H : p.W;
+void pm_launch_draws(const PmRunPlan& plan, int rot, const PmParams* dev_params, int batch, hipStream_t st) {
+  if (plan.sweep == kPmGeneric) return;
+  const int rw = (rot & 1) ? plan.H : plan.W;
   hipLaunchKernelGGL(pm_draw_kernel, dim3((rw + 63) / 64, batch, 1), dim3(64, 1, 1), 0, st, dev_params);
 }
 
-const char* pm_launch_sweep(const PmParams& p, const PmParams* dev_params, int batch, int threads, bool geom,
-                            bool filter_photo, bool filter_geom, hipStream_t st) {
-  const int rw = (p.rot & 1) ? p.H : p.W;
-  const unsigned groups = (unsigned)((rw + p.C - 1) / p.C);
-#define PM_LAUNCH_V4(KERNEL, MB, GRID, BLOCK, LDS)                                                   \
-  do {                                                                                              \
-    if (geom) {                                                                                     \
-      if (filter_photo && filter_geom) hipLaunchKernelGGL((KERNEL<true, true, true, MB>), GRID, BLOCK, LDS, st, dev_params);  \
-      else hipLaunchKernelGGL((KERNEL<true, false, false, MB>), GRID, BLOCK, LDS, st, dev_params);  \
-    } else {                                                                                        \
-      if (filter_photo) hipLaunchKernelGGL((KERNEL<false, true, false, MB>), GRID, BLOCK, LDS, st, dev_params);  \
-      else hipLaunchKernelGGL((KERNEL<false, false, false, MB>), GRID, BLOCK, LDS, st, dev_params); \
-    }                                                                                               \
-  } while (0)
-  if (pm_sweep_takes_wave_kernel(p, geom)) {   // (pm_launch_draws has run in front of this launch)
-    // COLMAP_AMD_PM_FP_GLOBAL=1 (tests): explicit indices although the buffer resource would do
-    const bool mubuf = pm_fp_resource_ok(p) && dev_switch_int("COLMAP_AMD_PM_FP_GLOBAL", 0) == 0;
-    const size_t qlds = lds_offsets_wave(p.C, p.S, p.radius, p.ntaps, p.num_samples, geom, kQuadThCap, kQuadWaves).total;
-    const dim3 qgrid((groups + kQuadWaves - 1) / kQuadWaves, batch, 1), qblock(64 * kQuadWaves, 1, 1);
-    if (p.prof && mubuf && !geom) {
-      // phase profile (pm_enable_phase_profile): the shipped kernel with its phase clocks compiled in
-      if (filter_photo) hipLaunchKernelGGL(pm_sweep_quad_prof_kernel<true>, qgrid, qblock, qlds, st, dev_params);
-      else hipLaunchKernelGGL(pm_sweep_quad_prof_kernel<false>, qgrid, qblock, qlds, st, dev_params);
-      return "pm_sweep_quad_prof_kernel";
-    }
-    if (p.help > 1 && mubuf && p.C == 1) {
-      const size_t plds = lds_offsets_wave(p.C, p.S, p.radius, p.ntaps, p.num_samples, geom, kQuadThCap, 1).total;
-      const dim3 pgrid(groups, batch, 1), pblock(128, 1, 1);
-      if (geom) {
-        if (filter_photo && filter_geom) hipLaunchKernelGGL((pm_sweep_pair_kernel<true, true, true>), pgrid, pblock, plds, st, dev_params);
-        else hipLaunchKernelGGL((pm_sweep_pair_kernel<true, false, false>), pgrid, pblock, plds, st, dev_params);
-      } else {
-        if (filter_photo) hipLaunchKernelGGL((pm_sweep_pair_kernel<false, true, false>), pgrid, pblock, plds, st, dev_params);
-        else hipLaunchKernelGGL((pm_sweep_pair_kernel<false, false, false>), pgrid, pblock, plds, st, dev_params);
-      }
-      return "pm_sweep_pair_kernel";
-    }
-    if (mubuf) PM_LAUNCH_V4(pm_sweep_quad_kernel, true, qgrid, qblock, qlds);
-    else PM_LAUNCH_V4(pm_sweep_quad_kernel, false, qgrid, qblock, qlds);
-    return mubuf ? "pm_sweep_quad_kernel" : "pm_sweep_quad_kernel (explicit indices)";
-  }
-#undef PM_LAUNCH_V4
-  const size_t lds = pm_sweep_lds_bytes(p, geom);
-  dim3 block(threads, 1, 1);
-  dim3 grid(groups, batch, 1);
-#define PM_LAUNCH_N(N, G, FP, FG, PR) \
-  hipLaunchKernelGGL((pm_sweep_kernel<N, G, FP, FG, PR>), grid, block, lds, st, dev_params)
+// The four legal (GEOM, FILTER_PHOTO, FILTER_GEOM) instantiations of a sweep kernel: the geometric pass filters by both
+// criteria or not at all, the photometric pass by the photometric one or not at all. f(geom, filter_photo, filter_geom)
+// receives them as std::bool_constant values.
+template <typename F>
+static void with_filter_variant(bool geom, bool filter_photo, bool filter_geom, F&& f) {
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
   if (geom) {
-    if (filter_photo && filter_geom) PM_LAUNCH_N(0, true, true, true, false);
-    else PM_LAUNCH_N(0, true, false, false, false);
+    if (filter_photo && filter_geom) f(yes, yes, yes);
+    else f(yes, no, no);
   } else {
-    if (filter_photo) PM_LAUNCH_N(0, false, true, false, false);
-    else PM_LAUNCH_N(0, false, false, false, false);
+    if (filter_photo) f(no, yes, no);
+    else f(no, no, no);
   }
-#undef PM_LAUNCH_N
-  return "pm_sweep_kernel";
+}
+
+void pm_launch_sweep(const PmRunPlan& plan, int rot, const PmParams* dev_params, int batch, bool filter_photo,
+                     bool filter_geom, hipStream_t st) {
+  const int rw = (rot & 1) ? plan.H : plan.W;
+  const unsigned groups = (unsigned)((rw + plan.C - 1) / plan.C);
+  const bool quads = plan.sweep == kPmQuad || plan.sweep == kPmQuadProf;  // four column groups per workgroup
+  const dim3 grid(quads ? (groups + kQuadWaves - 1) / kQuadWaves : groups, batch, 1), block(plan.sweep_block, 1, 1);
+  const size_t lds = plan.sweep_lds;
+  with_filter_variant(plan.geom, filter_photo, filter_geom, [&](auto geom, auto fphoto, auto fgeom) {
+    constexpr bool G = decltype(geom)::value, FP = decltype(fphoto)::value, FG = decltype(fgeom)::value;
+    switch (plan.sweep) {
+      case kPmGeneric:
+        hipLaunchKernelGGL((pm_sweep_kernel<G, FP, FG>), grid, block, lds, st, dev_params);
+        break;
+      case kPmQuad:   // (pm_launch_draws has run in front of the wave kernels' launches)
+        if (plan.fp_resource) hipLaunchKernelGGL((pm_sweep_quad_kernel<G, FP, FG, true>), grid, block, lds, st, dev_params);
+        else hipLaunchKernelGGL((pm_sweep_quad_kernel<G, FP, FG, false>), grid, block, lds, st, dev_params);
+        break;
+      case kPmPair:
+        hipLaunchKernelGGL((pm_sweep_pair_kernel<G, FP, FG>), grid, block, lds, st, dev_params);
+        break;
+      case kPmQuadProf:   // photometric sweeps only (pm_plan_run)
+        if constexpr (!G) hipLaunchKernelGGL(pm_sweep_quad_prof_kernel<FP>, grid, block, lds, st, dev_params);
+        break;
+    }
+  });
 }
 void pm_launch_rng_streams(const unsigned long long* seeds, int nseeds, int ndraws, float* out,
                            hipStream_t st) {

@@ -185,7 +185,8 @@ int pm_copy_maps_to_device(pm_handle* h, float* depth_dev, float* normal_dev);
  * messages, 1 tile scroll, 2 hypotheses, 3 patch weights, 4 priors, 5 CDF, 6 draws, 7 task lists, 8-10 hypothesis
  * NCC (homographies, tap rounds, normalisation), 11-13 sums / argmin / winner tasks, 14-16 winner NCC, 17 messages and
  * record stores, 18 filter + row end, 23 = number of waves that reported. pm_get_phase_profile returns the first ten
- * (the generic kernel's coarser split when that kernel ran). */
+ * of them. Runs that the profiling kernel does not serve (other windows, the geometric pass, explicit indices: see
+ * pm_get_sweep_kernel_name) run unprofiled and leave every counter zero. */
 #define PM_PROFILE_SLOTS 24
 int pm_enable_phase_profile(pm_handle* h, int enable);
 int pm_get_phase_profile(pm_handle* h, unsigned long long* out10);

@@ -134,6 +134,19 @@ def test_generic_kernel_other_windows(pm_oracle, radius, step):
     assert pm.GetSweepKernelName() == "pm_sweep_kernel"
 
 
+@pytest.mark.parametrize("case", ["initial_cost", "photometric"])
+def test_generic_family_at_default_window(pm_oracle, request, case):
+    """COLMAP_AMD_PM_WAVE=0: pm_initial_cost_kernel and pm_sweep_kernel at the 11 x 11 window (ragged width 35)."""
+    G.check_generic_family_at_default_window(pm_oracle, request, scene(4, 35, 27), 1, [0, 2, 3], case)
+
+
+@pytest.mark.parametrize("radius", [5, 2])
+def test_phase_profile(pm_oracle, radius):
+    """pm_sweep_quad_prof_kernel at the default window (the stand-in's cycle counter is the host's); at the 5 x 5 window
+    the unprofiled generic kernel and all-zero slots."""
+    G.check_phase_profile(pm_oracle, scene(4, 35, 27), 1, [0, 2, 3], radius)
+
+
 def test_baseline_source_count_s20_m15(pm_oracle):
     """S = 20 sources, M = 15 samples (BASELINE config[1]'s LDS layout and task lists) on a tiny image, two sweeps."""
     views = scene(21, 24, 18, 3.6 * 20)

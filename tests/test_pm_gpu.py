@@ -20,13 +20,17 @@ from colmap_amd import synthetic as syn
 pytestmark = pytest.mark.gpu
 
 
-def _run_both(pm_oracle, views, ref, src, maps=None, **kw):
+def _run_both(pm_oracle, views, ref, src, maps=None, prepare=None, **kw):
+    """`prepare(pm)`: called on the created handle before the run."""
     from colmap_amd import mvs
     dmin, dmax = syn.depth_range(views, ref)
     o, h = paired_options(pm_oracle, depth_min=dmin, depth_max=dmax, **kw)
     imgs = oracle_inputs(views, maps is not None, maps)
     want = pm_oracle.run(o, imgs, ref, src, want_cost=True)
     pm = mvs.PatchMatch(h, hip_problem(views, ref, src, maps))
+    if prepare is not None:
+        pm.Create()
+        prepare(pm)
     pm.Run()
     got = dict(depth=pm.GetDepthMap(), normal=pm.GetNormalMap(), sel_prob=pm.GetSelProbMap(),
                cost=pm.GetCostMap(), mask=pm.GetConsistencyMask())
@@ -177,6 +181,60 @@ def test_generic_kernel_equals_wave_kernels(pm_oracle, wave):
                               window_radius=radius)
     _assert_equal(want, got)
     assert pm.GetSweepKernelName() == ("pm_sweep_kernel" if wave == "0" else "pm_sweep_quad_kernel")
+
+
+def check_generic_family_at_default_window(pm_oracle, request, views, ref, src, case):
+    """COLMAP_AMD_PM_WAVE=0 (the A/B reference): the generic family -- pm_initial_cost_kernel, pm_sweep_kernel -- at the
+    default 11 x 11 window, where the wave kernels would run; 121 taps are no multiple of 16, so the zero-weight tail of
+    the chunk of 128 is exercised. Shared with the stand-in (tests/test_pm_emul.py), which passes its own shape."""
+    from colmap_amd import mvs
+    from switches import set_switch
+    lib = mvs.lib()
+    set_switch(lib, "COLMAP_AMD_PM_WAVE", "0")
+    request.addfinalizer(lambda: set_switch(lib, "COLMAP_AMD_PM_WAVE", None))
+    if case == "initial_cost":   # no sweep: the cost map is pm_initial_cost_kernel's
+        want, got, pm = _run_both(pm_oracle, views, ref, src, geom_consistency=0, filter=0, max_sweeps=0)
+        _assert_equal(want, got, ("depth", "normal", "cost"))
+        return
+    maps = [(v.depth.copy(), v.normal.copy()) for v in views] if case == "geometric" else None
+    want, got, pm = _run_both(pm_oracle, views, ref, src, maps=maps, geom_consistency=int(case == "geometric"), filter=1,
+                              num_iterations=1)
+    _assert_equal(want, got)
+    assert pm.GetSweepKernelName() == "pm_sweep_kernel"
+
+
+@pytest.mark.parametrize("case", ["initial_cost", "photometric", "geometric"])
+def test_generic_family_at_default_window(pm_oracle, request, case):
+    """Ragged width (67 columns, four per group), S = 4; the geometric pass with both filters."""
+    check_generic_family_at_default_window(pm_oracle, request, scene(5, 67, 45), 2, [0, 1, 3, 4], case)
+
+
+def check_phase_profile(pm_oracle, views, ref, src, radius):
+    """EnablePhaseProfile on one photometric iteration. Default window: the run launches the profiling build of the
+    four-wave kernel, whose waves each report once (last slot). 5 x 5 window: the generic kernel has no phase clocks,
+    the run is unprofiled and every slot stays zero. Either way the maps are the unprofiled run's bits = the oracle's."""
+    from colmap_amd import mvs
+    kw = dict(geom_consistency=0, filter=1, num_iterations=1, window_radius=radius)
+    want, plain, pm0 = _run_both(pm_oracle, views, ref, src, **kw)
+    _, got, pm = _run_both(pm_oracle, views, ref, src, prepare=lambda pm: pm.EnablePhaseProfile(True), **kw)
+    _assert_equal(want, plain)
+    _assert_equal(want, got)
+    slots = (C.c_ulonglong * 24)()
+    assert mvs.lib().pm_get_phase_profile_slots(pm._h, slots, 24) == 0
+    slots = list(slots)
+    if radius == 5:
+        assert pm0.GetSweepKernelName() == "pm_sweep_quad_kernel"
+        assert pm.GetSweepKernelName() == "pm_sweep_quad_prof_kernel"
+        assert slots[23] > 0, slots                 # waves that reported
+        assert pm.GetPhaseProfile() == slots[:10]
+    else:
+        assert pm0.GetSweepKernelName() == pm.GetSweepKernelName() == "pm_sweep_kernel"
+        assert slots == [0] * 24, slots
+
+
+@pytest.mark.parametrize("radius", [5, 2])
+def test_phase_profile(pm_oracle, radius):
+    check_phase_profile(pm_oracle, scene(5, 67, 45), 2, [0, 1, 3, 4], radius)
 
 
 def test_single_source_and_many_samples(pm_oracle):
