@@ -35,6 +35,8 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include "ba_layout.h"  // after the HIP header: the camera-model table gets its host/device qualifiers
+
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -51,6 +53,13 @@
 #include <vector>
 
 using colmap_amd::dev_switch_int;
+using ba_layout::KD_MAX;
+using ba_layout::NPAR;
+using ba_layout::TIER_MAX;
+using ba_layout::TIER_NARROW;
+using ba_layout::TIER_WIDE;
+using ba_layout::model_supported;
+using ba_layout::num_params_of;
 
 extern "C" void pm_release_cached_memory(void);  // pm_api.cpp (same library)
 
@@ -77,10 +86,8 @@ constexpr int PD = 6;        // pose tangent width (5 when the gauge holds a tra
 // more than 4 variable intrinsics (every model with the principal point fixed except OPENCV), else
 // <8, 8>, or <16, 16> (below). The kernels whose register footprint depends on them are templates
 // (instantiated through Solver::with_tier); the others read V.kd / V.bd.
-constexpr int KD_MAX = 8;
 constexpr int KD_WIDE = 16;  // FULL_OPENCV / THIN_PRISM_FISHEYE (12), RAD_TAN_THIN_PRISM_FISHEYE (16): third <KD, BD> tier
 constexpr int NPAR_WIDE = 16;
-constexpr int NPAR = 8;      // max number of parameters of a supported camera model (J_params is 2 x NPAR)
 static int chunk_size() {     // observations per camera-side reduction chunk (one wave each)
   const int v = dev_switch_int("COLMAP_AMD_BA_CHUNK", 512);
   return v >= 64 ? v : 512;
@@ -235,26 +242,6 @@ __device__ __forceinline__ void atomic_max_pos(double* addr, double v) {
 // ------------------------------------------------------------------------------------------
 // Per-residual math (reference reprojection_error.h:68-134)
 // ------------------------------------------------------------------------------------------
-__device__ __host__ __forceinline__ int num_params_of(int model) {
-  switch (model) {
-    case BA_SIMPLE_PINHOLE: case BA_SIMPLE_FISHEYE: return 3;
-    case BA_RADIAL: case BA_RADIAL_FISHEYE: case BA_FOV: case BA_DIVISION: return 5;
-    case BA_EUCM: return 6;
-    case BA_OPENCV: case BA_OPENCV_FISHEYE: return 8;
-    case BA_FULL_OPENCV: case BA_THIN_PRISM_FISHEYE: return 12;
-    case BA_RAD_TAN_THIN_PRISM_FISHEYE: return 16;
-    case BA_EQUIRECTANGULAR: return 2;
-    default: return 4;  // PINHOLE, SIMPLE_RADIAL, SIMPLE_RADIAL_FISHEYE, SIMPLE_DIVISION, FISHEYE
-  }
-}
-__host__ inline bool model_supported(int model) {
-  return model == BA_SIMPLE_PINHOLE || model == BA_PINHOLE || model == BA_SIMPLE_RADIAL || model == BA_RADIAL ||
-         model == BA_OPENCV || model == BA_OPENCV_FISHEYE || model == BA_SIMPLE_RADIAL_FISHEYE ||
-         model == BA_RADIAL_FISHEYE || model == BA_FOV || model == BA_SIMPLE_DIVISION || model == BA_DIVISION ||
-         model == BA_SIMPLE_FISHEYE || model == BA_FISHEYE || model == BA_EUCM || model == BA_FULL_OPENCV ||
-         model == BA_THIN_PRISM_FISHEYE || model == BA_RAD_TAN_THIN_PRISM_FISHEYE || model == BA_EQUIRECTANGULAR;
-}
-
 // QuaternionRotatePointWithJac, quaternion_utils.h:105-153
 __device__ __forceinline__ void quat_rotate(const double* q, const double* p, double out[3], double* J) {
   const double qx = q[0], qy = q[1], qz = q[2], qw = q[3];
@@ -3003,9 +2990,10 @@ struct Buf {
     BA_HIP(e_alloc);
     BA_HIP(hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T)));
   }
-  void upload(const std::vector<T>& h) {
+  T* upload(const std::vector<T>& h) {  // returns the device pointer: an upload and its view field are one statement
     alloc(h.size());
     if (!h.empty()) BA_HIP(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    return p;
   }
   // non-owning window into another buffer (sub-vectors of one all-reduce payload)
   void alias(T* ptr, size_t count) {
@@ -3051,22 +3039,6 @@ struct Event {
 
 inline int grid_for(size_t n, int block) { return (int)((n + block - 1) / block); }
 
-// Host-side set-up loops over the observations (gathers into the device orders: random reads that one core serves at
-// a cache miss a time): contiguous index ranges on up to 16 threads. fn(begin, end, thread).
-template <typename F>
-inline void host_parallel_for(int64_t n, F&& fn) {
-  const int64_t grain = 1 << 16;
-  int T = (int)std::min<int64_t>(std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u), (n + grain - 1) / grain);
-  if (T <= 1) {
-    fn((int64_t)0, n, 0);
-    return;
-  }
-  std::vector<std::thread> th;
-  th.reserve(T);
-  for (int t = 0; t < T; ++t) th.emplace_back([&, t] { fn(n * t / T, n * (t + 1) / T, t); });
-  for (auto& x : th) x.join();
-}
-
 // sync + check after every launch; read per launch (an atomic load unless some switch is set), so that
 // colmap_amd_set_switch("COLMAP_AMD_BA_DEBUG", "1") takes effect whenever it is called
 static inline bool ba_debug() { return dev_switch_int("COLMAP_AMD_BA_DEBUG", 0) != 0; }
@@ -3087,7 +3059,6 @@ template <int KD_, int BD_, int KDT_>
 struct Tier {
   static constexpr int kd = KD_, bd = BD_, kdt = KDT_;
 };
-enum TierId { TIER_NARROW, TIER_MAX, TIER_WIDE };
 struct CovHandle;
 
 struct Solver {
@@ -3100,7 +3071,6 @@ struct Solver {
   // topology
   Buf<int> o_sensor, sens_off;
   Buf<double> sensors, sensors2, Jsens;
-  std::vector<int> h_sens_off;
   Buf<int> o_pose, o_cam, o_pt, pose_off, pose_dim, pose_fix, cam_off, cam_dim, cam_var, cam_model, pt_off,
       pt_ptr, blk_off, blk_dim, blk_kind, blk_moff, chunk_blk, chunk_beg, chunk_end, blk_chunk_ptr, blk_fin_end, heavy_blk, c2a, a2c, tile_pt;
   Buf<int4> tile_info;
@@ -3143,14 +3113,14 @@ struct Solver {
   PriorView Q{};
   bool use_dense = false;
   bool use_priors() const { return Q.n > 0 && comm.rank == 0; }  // sums are all-reduced: one rank contributes them
-  int moff_total = 0;
-  long long n_paired = 0;  // (observation, block kind) slots that have a partner of the same point in the block
-  long long n_paired_kind[3] = {0, 0, 0};
   Buf<int> a_boff[3];
   Buf<double> Wp[3];
   int width_tier = TIER_NARROW;  // <KD, BD> of this problem, chosen in build()
   int kd = 4, bd = PD;           // its intrinsics tangent width / widest camera-side block
-  std::vector<int> h_pose_off, h_cam_off, h_pt_off;
+  // the host-built layout (ba_layout.h). After build() only its small maps are left: offsets and dimensions, blk_of_*,
+  // blk_off / blk_moff, the priors' po / so; keep_obs_maps (set before build(): the step probe) keeps obs_of_a and a2c
+  ba_layout::Layout lay;
+  bool keep_obs_maps = false;
   Event ev0, ev1, ev2, ev3;
   Stream st_chol;  // second stream + events of the Cholesky lookahead (exact tiers)
   ba_explicit::PairLists pair_lists;  // pair-major formation of the exact tiers (built with the solve's other structures)
@@ -3215,7 +3185,8 @@ struct Solver {
   }
   void zero_scalar(int slot) { BA_HIP(hipMemsetAsync(scalars.p + slot, 0, sizeof(double), st)); }
 
-  // Reduced program: active observations (>= 1 variable block), tangent offsets, CSR structures.
+  // Reduced program: active observations (>= 1 variable block), tangent offsets, CSR structures -- the layout is
+  // built on the host (ba_layout.h), then uploaded.
   int build(ba_result* res_out) {
     const ba_problem& p = prob;
     // COLMAP_AMD_BA_TIMING=1 (development switch): where the set-up time goes, to stderr
@@ -3227,512 +3198,169 @@ struct Solver {
       std::fprintf(stderr, "[ba set-up] %-14s %8.2f ms\n", name, 1e3 * std::chrono::duration<double>(now - t_stage).count());
       t_stage = now;
     };
-    std::vector<int> cam_nvar(p.num_cams, 0);
-    std::vector<int> wide_cam_var((size_t)p.num_cams * KD_WIDE, 0), h_cam_dim(p.num_cams, 0);
-    int max_nvar = 0, max_npar = 0;
-    for (int k = 0; k < p.num_cams; ++k) {
-      const int model = p.cam_model[k];
-      if (!model_supported(model))
-        throw std::runtime_error("unsupported camera model id " + std::to_string(model) +
-                                 " (supported: SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, "
-                                 "OPENCV_FISHEYE, FOV, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE, SIMPLE_DIVISION, "
-                                 "DIVISION, SIMPLE_FISHEYE, FISHEYE, EUCM, FULL_OPENCV, THIN_PRISM_FISHEYE, "
-                                 "RAD_TAN_THIN_PRISM_FISHEYE, EQUIRECTANGULAR)");
-      const int P = num_params_of(model);
-      for (int j = 0; j < P; ++j)
-        if (!p.cam_const[(size_t)k * BA_CAM_STRIDE + j]) wide_cam_var[(size_t)k * KD_WIDE + cam_nvar[k]++] = j;
-      max_nvar = std::max(max_nvar, cam_nvar[k]);
-      max_npar = std::max(max_npar, P);
-    }
-    // <KD, BD> of this problem (see the constants at the top of the file); a 12-parameter model takes
-    // the wide tier whatever its number of variable intrinsics (only that tier evaluates 12 J_params columns)
-    width_tier = max_npar > NPAR || max_nvar > KD_MAX ? TIER_WIDE : (max_nvar <= 4 ? TIER_NARROW : TIER_MAX);
+    ba_layout::LayoutParams lp;
+    lp.rank = comm.rank; lp.world = comm.world; lp.by_point = comm.by_point;
+    lp.chunk = chunk_size();
+    lp.heavy_chunks = std::max(dev_switch_int("COLMAP_AMD_BA_HEAVY_CHUNKS", kHeavyChunks), 1);
+    lp.tile_pts = TILE_PTS; lp.tile_obs = TILE_OBS;
+    lp.inc_chunk = kIncChunk; lp.pair_chunk = kPairChunk;
+    lp.pair_incidences = dev_switch_int("COLMAP_AMD_BA_PAIR_INCIDENCES", 1) != 0;
+    lp.stage = stage;
+    lay = ba_layout::make_layout(p, lp);
+    // <KD, BD> of this problem (see the constants at the top of the file)
+    width_tier = ba_layout::pick_tier(lay);
     with_tier([&](auto t) { kd = t.kd; bd = t.bd; });
-    std::vector<int> h_cam_var((size_t)p.num_cams * kd, 0);
-    for (int k = 0; k < p.num_cams; ++k)
-      for (int d = 0; d < cam_nvar[k]; ++d) h_cam_var[(size_t)k * kd + d] = wide_cam_var[(size_t)k * KD_WIDE + d];
-    std::vector<int64_t> active;
-    active.reserve(p.num_obs / comm.world + 1);
-    int64_t n_active_global = 0;
-    std::vector<char> pose_used(p.num_poses, 0), cam_used(p.num_cams, 0), pt_used(p.num_points, 0),
-        sens_used(std::max(p.num_sensors, 0) + 1, 0);
-    for (int64_t o = 0; o < p.num_obs; ++o) {
-      const int pi = p.obs_pose[o], ci = p.obs_cam[o], xi = p.obs_point[o];
-      if (pi < 0 || pi >= p.num_poses || ci < 0 || ci >= p.num_cams || xi < 0 || xi >= p.num_points)
-        throw std::runtime_error("observation index out of range");
-      if (p.obs_sensor && (p.obs_sensor[o] < -1 || p.obs_sensor[o] >= p.num_sensors))
-        throw std::runtime_error("observation sensor index out of range");
-      const int sv = p.obs_sensor ? p.obs_sensor[o] : -1;
-      const bool sens_var = sv >= 0 && p.sensor_const != nullptr && !p.sensor_const[sv];
-      if (p.pose_const[pi] && cam_nvar[ci] == 0 && p.point_const[xi] && !sens_var) continue;
-      ++n_active_global;
-      pose_used[pi] = cam_used[ci] = pt_used[xi] = 1;  // layout = all ranks' observations
-      if (sens_var) sens_used[sv] = 1;
-      // image sharding (BASELINE.json: "images shard across the GPUs") or point sharding (every
-      // observation of a point on one rank: the point-side quantities stay local)
-      if ((comm.by_point ? xi : pi) % comm.world == comm.rank) active.push_back(o);
-    }
-    const int n = (int)active.size();
-    stage("scan");
-    // The two orders of the observations, by stable COUNTING sorts (the keys are block indices; comparison sorts of
-    // 2 M ... 20 M observations were most of the 0.3 s ... 5.5 s a solve spent before its first kernel):
-    // p-order: sorted by point (stable: keeps the caller's order inside a track)
-    std::vector<int> h_pt_ptr(p.num_points + 1, 0);
-    for (int a = 0; a < n; ++a) h_pt_ptr[p.obs_point[active[a]] + 1]++;
-    for (int j = 0; j < p.num_points; ++j) h_pt_ptr[j + 1] += h_pt_ptr[j];
-    {
-      std::vector<int> cursor(h_pt_ptr.begin(), h_pt_ptr.end() - 1);
-      std::vector<int64_t> sorted((size_t)n);
-      for (int a = 0; a < n; ++a) sorted[(size_t)cursor[p.obs_point[active[a]]]++] = active[a];
-      active.swap(sorted);
-    }
-    // c-order: p-order positions sorted by (camera, pose) -> every camera-side block is a range. Least significant
-    // key first: stable by pose, then stable by camera; ties keep the p-order (what std::stable_sort on the pair gave).
-    std::vector<int> h_c2a(n), h_a2c(n);
-    {
-      std::vector<int> by_pose((size_t)n), cnt((size_t)std::max(p.num_poses, p.num_cams) + 1, 0);
-      for (int a = 0; a < n; ++a) cnt[(size_t)p.obs_pose[active[a]] + 1]++;
-      for (int i = 0; i < p.num_poses; ++i) cnt[(size_t)i + 1] += cnt[i];
-      for (int a = 0; a < n; ++a) by_pose[(size_t)cnt[p.obs_pose[active[a]]]++] = a;
-      std::fill(cnt.begin(), cnt.end(), 0);
-      for (int a = 0; a < n; ++a) cnt[(size_t)p.obs_cam[active[a]] + 1]++;
-      for (int k = 0; k < p.num_cams; ++k) cnt[(size_t)k + 1] += cnt[k];
-      for (int i = 0; i < n; ++i) {
-        const int a = by_pose[i];
-        h_c2a[(size_t)cnt[p.obs_cam[active[a]]]++] = a;
-      }
-    }
-    for (int c = 0; c < n; ++c) h_a2c[h_c2a[c]] = c;
-    stage("orders");
-    // point tiles for the LDS-staged point passes
-    std::vector<int> h_tile_pt;
-    {
-      bool ok = true;
-      int j = 0;
-      h_tile_pt.push_back(0);
-      while (j < p.num_points) {
-        int j1 = j, obs = 0;
-        while (j1 < p.num_points && j1 - j < TILE_PTS && obs + (h_pt_ptr[j1 + 1] - h_pt_ptr[j1]) <= TILE_OBS) {
-          obs += h_pt_ptr[j1 + 1] - h_pt_ptr[j1];
-          ++j1;
-        }
-        if (j1 == j) { ok = false; break; }  // a single track longer than a tile
-        h_tile_pt.push_back(j1);
-        j = j1;
-      }
-      if (!ok) h_tile_pt.assign(1, 0);
-    }
-    // the same topology in p-order (position a <-> c-order position h_a2c[a])
-    {
-      split_linearize = dev_switch_int("COLMAP_AMD_BA_SPLIT_LINEARIZE", 1) != 0;  // read per solve: tests toggle it
-    }
-    const bool has_sensors = p.obs_sensor != nullptr && p.num_sensors > 0 && p.sensors != nullptr;
-    std::vector<int> h_a_pose, h_a_cam, h_a_pt, h_a_sensor;
-    std::vector<double> h_a_xy;
-    {  // (the explicit Schur formation reads it too, whatever the linearisation does)
-      h_a_pose.resize(n); h_a_cam.resize(n); h_a_pt.resize(n); h_a_xy.resize((size_t)2 * n);
-      if (has_sensors) h_a_sensor.resize(n);
-      host_parallel_for(n, [&](int64_t a0, int64_t a1, int) {
-        for (int64_t a = a0; a < a1; ++a) {
-          const int64_t o = active[a];
-          h_a_pose[a] = p.obs_pose[o];
-          h_a_cam[a] = p.obs_cam[o];
-          h_a_pt[a] = p.obs_point[o];
-          h_a_xy[2 * (size_t)a] = p.obs_xy[2 * o];
-          h_a_xy[2 * (size_t)a + 1] = p.obs_xy[2 * o + 1];
-          if (has_sensors) h_a_sensor[a] = p.obs_sensor[o];
-        }
-      });
-    }
-    // solo flags: does another observation of the same point use the same pose / camera? (a track's entries of the
-    // p-order arrays are neighbours in memory: the quadratic loop over a track stays in cache)
-    std::vector<unsigned char> h_solo(n, 0);
-    {
-      long long paired_t[16][4] = {};   // per thread: n_paired, n_paired_kind[0..2]
-      host_parallel_for(p.num_points, [&](int64_t j0, int64_t j1, int t) {
-        long long* acc = paired_t[t];
-        for (int64_t j = j0; j < j1; ++j)
-          for (int a = h_pt_ptr[j]; a < h_pt_ptr[j + 1]; ++a) {
-            int same_pose = 0, same_cam = 0, same_sens = 0;
-            const int sa = has_sensors ? h_a_sensor[a] : (p.obs_sensor ? p.obs_sensor[active[a]] : -1);
-            const int pose_a = h_a_pose[a], cam_a = h_a_cam[a];
-            for (int a2 = h_pt_ptr[j]; a2 < h_pt_ptr[j + 1]; ++a2) {
-              same_pose += h_a_pose[a2] == pose_a;
-              same_cam += h_a_cam[a2] == cam_a;
-              same_sens += sa >= 0 && (has_sensors ? h_a_sensor[a2] : p.obs_sensor[active[a2]]) == sa;
-            }
-            h_solo[h_a2c[a]] = (unsigned char)((same_pose == 1 ? 1 : 0) | (same_cam == 1 ? 2 : 0) | (same_sens <= 1 ? 4 : 0));
-            const int k0 = same_pose != 1 && !p.pose_const[pose_a];
-            const int k1 = same_cam != 1 && cam_nvar[cam_a] > 0;
-            const int k2 = same_sens > 1 && sens_used[sa];
-            acc[0] += k0 + k1 + k2;
-            acc[1] += k0;
-            acc[2] += k1;
-            acc[3] += k2;
-          }
-      });
-      for (int t = 0; t < 16; ++t) {
-        n_paired += paired_t[t][0];
-        for (int k = 0; k < 3; ++k) n_paired_kind[k] += paired_t[t][1 + k];
-      }
-    }
-    std::vector<int> h_o_pose(n), h_o_cam(n), h_o_pt(n), h_o_sensor;
-    if (has_sensors) h_o_sensor.resize(n);
-    std::vector<double> h_xy((size_t)2 * n);
-    host_parallel_for(n, [&](int64_t c0, int64_t c1, int) {
-      for (int64_t c = c0; c < c1; ++c) {
-        const int a = h_c2a[c];   // c-order from the p-order copies: one indirection, 4-byte indices
-        if (has_sensors) h_o_sensor[c] = h_a_sensor[a];
-        h_o_pose[c] = h_a_pose[a];
-        h_o_cam[c] = h_a_cam[a];
-        h_o_pt[c] = h_a_pt[a];
-        h_xy[2 * (size_t)c] = h_a_xy[2 * (size_t)a];
-        h_xy[2 * (size_t)c + 1] = h_a_xy[2 * (size_t)a + 1];
-      }
-    });
-    stage("topology");
-    // tangent layout: pose blocks, then intrinsics blocks (camera side); points
-    h_pose_off.assign(p.num_poses, -1);
-    h_cam_off.assign(p.num_cams, -1);
-    h_pt_off.assign(p.num_points, -1);
-    std::vector<int> h_pose_dim(p.num_poses, 0), h_pose_fix(p.num_poses, -1);
-    std::vector<int> h_blk_off, h_blk_dim, h_blk_kind, h_blk_moff;
-    std::vector<int> blk_of_pose(p.num_poses, -1), blk_of_cam(p.num_cams, -1);
-    int off = 0, moff = 0;
-    for (int i = 0; i < p.num_poses; ++i) {
-      if (p.pose_const[i] || !pose_used[i]) continue;
-      const int pf = p.pose_fixed_t[i];
-      if (pf < -1 || pf > 7) throw std::runtime_error("pose_fixed_t out of range");
-      h_pose_fix[i] = pf;
-      h_pose_dim[i] = (pf >= 4 ? 0 : 3) + ((pf >= 0 && (pf & 3) != 3) ? 2 : 3);
-      h_pose_off[i] = off;
-      blk_of_pose[i] = (int)h_blk_off.size();
-      h_blk_off.push_back(off); h_blk_dim.push_back(h_pose_dim[i]); h_blk_kind.push_back(0);
-      h_blk_moff.push_back(moff);
-      off += h_pose_dim[i];
-      moff += h_pose_dim[i] * h_pose_dim[i];
-    }
-    for (int k = 0; k < p.num_cams; ++k) {
-      if (cam_nvar[k] == 0 || !cam_used[k]) continue;
-      h_cam_dim[k] = cam_nvar[k];
-      h_cam_off[k] = off;
-      blk_of_cam[k] = (int)h_blk_off.size();
-      h_blk_off.push_back(off); h_blk_dim.push_back(cam_nvar[k]); h_blk_kind.push_back(1);
-      h_blk_moff.push_back(moff);
-      off += cam_nvar[k];
-      moff += cam_nvar[k] * cam_nvar[k];
-    }
-    // variable sensor_from_rig blocks (RigReprojErrorCostFunctor's cam_from_rig parameter block,
-    // bundle_adjustment_ceres.cc:804-812): full 6-dimensional pose tangent, block kind 2
-    h_sens_off.assign(std::max(p.num_sensors, 0), -1);
-    std::vector<int> blk_of_sens(std::max(p.num_sensors, 0), -1);
-    int n_var_sensors = 0;
-    for (int sidx = 0; sidx < p.num_sensors; ++sidx) {
-      if (!sens_used[sidx]) continue;
-      h_sens_off[sidx] = off;
-      blk_of_sens[sidx] = (int)h_blk_off.size();
-      h_blk_off.push_back(off); h_blk_dim.push_back(6); h_blk_kind.push_back(2);
-      h_blk_moff.push_back(moff);
-      off += 6;
-      moff += 36;
-      ++n_var_sensors;
-    }
-    const int n_c = off;
-    moff_total = moff;
-    int poff = 0;
-    for (int j = 0; j < p.num_points; ++j) {
-      if (p.point_const[j] || !pt_used[j]) continue;
-      h_pt_off[j] = poff;
-      poff += 3;
-    }
-    // per-block c-order runs, split into chunks. A camera's observations are one run (c-order is
-    // sorted by camera first); a pose seen through several cameras (a rig frame) owns one run per
-    // camera. Every chunk is a contiguous range of one block.
-    const int n_blk = (int)h_blk_off.size();
-    std::vector<std::vector<std::pair<int, int>>> runs(n_blk);
-    auto add_run = [&](int b, int c) {
-      if (b < 0) return;
-      auto& r = runs[b];
-      if (!r.empty() && r.back().second == c) r.back().second = c + 1;
-      else r.emplace_back(c, c + 1);
-    };
-    for (int c = 0; c < n; ++c) {
-      add_run(blk_of_pose[h_o_pose[c]], c);
-      add_run(blk_of_cam[h_o_cam[c]], c);
-      if (has_sensors && h_o_sensor[c] >= 0) add_run(blk_of_sens[h_o_sensor[c]], c);
-    }
-    const int CHUNK = chunk_size() & ~1;  // even: the MFMA Gram kernel consumes observation pairs
-    std::vector<int> h_chunk_blk, h_chunk_beg, h_chunk_end, h_blk_chunk_ptr(n_blk + 1, 0);
-    for (int b = 0; b < n_blk; ++b) {
-      h_blk_chunk_ptr[b] = (int)h_chunk_blk.size();
-      for (const auto& run : runs[b])
-        for (int s = run.first; s < run.second; s += CHUNK) {
-          h_chunk_blk.push_back(b);
-          h_chunk_beg.push_back(s);
-          h_chunk_end.push_back(std::min(s + CHUNK, run.second));
-        }
-    }
-    h_blk_chunk_ptr[n_blk] = (int)h_chunk_blk.size();
-    std::vector<int> h_blk_fin_end(std::max(n_blk, 1), 0), h_heavy;
-    const int heavy_chunks = std::max(dev_switch_int("COLMAP_AMD_BA_HEAVY_CHUNKS", kHeavyChunks), 1);
-    for (int b = 0; b < n_blk; ++b) {
-      const bool heavy = h_blk_chunk_ptr[b + 1] - h_blk_chunk_ptr[b] > heavy_chunks;
-      h_blk_fin_end[b] = heavy ? h_blk_chunk_ptr[b] + 1 : h_blk_chunk_ptr[b + 1];
-      if (heavy) h_heavy.push_back(b);
-    }
-
-    // position priors whose pose or sensor_from_rig block is variable
-    {
-      std::vector<int> q_pose, q_sens, q_po, q_so, q_pdim;
-      std::vector<double> q_pos, q_A;
-      std::vector<std::array<int, 3>> targets;  // block, prior, first column
-      if (p.num_priors < 0) throw std::runtime_error("num_priors < 0");
-      for (int k = 0; k < p.num_priors; ++k) {
-        const int pi = p.prior_pose[k];
-        const int si = p.prior_sensor ? p.prior_sensor[k] : -1;
-        if (pi < 0 || pi >= p.num_poses || si < -1 || si >= p.num_sensors) throw std::runtime_error("prior index out of range");
-        const int po = h_pose_off[pi], so = si >= 0 ? h_sens_off[si] : -1;
-        if (po < 0 && so < 0) continue;
-        const int kk = (int)q_pose.size();
-        const int pdim = po >= 0 ? h_pose_dim[pi] : 0;
-        q_pose.push_back(pi); q_sens.push_back(si); q_po.push_back(po); q_so.push_back(so); q_pdim.push_back(pdim);
-        q_pos.insert(q_pos.end(), p.prior_position + 3 * (size_t)k, p.prior_position + 3 * (size_t)k + 3);
-        q_A.insert(q_A.end(), p.prior_sqrt_info + 9 * (size_t)k, p.prior_sqrt_info + 9 * (size_t)k + 9);
-        if (po >= 0) targets.push_back({blk_of_pose[pi], kk, 0});
-        if (so >= 0) targets.push_back({blk_of_sens[si], kk, pdim});
-      }
-      Q = PriorView{};
-      Q.n = (int)q_pose.size();
-      if (Q.n > 0) {
-        if (p.prior_loss_type < BA_LOSS_TRIVIAL || p.prior_loss_type > BA_LOSS_HUBER || !(p.prior_loss_scale > 0.0))
-          throw std::runtime_error("prior loss type / scale");
-        std::stable_sort(targets.begin(), targets.end(), [](const std::array<int, 3>& a, const std::array<int, 3>& b) { return a[0] < b[0]; });
-        std::vector<int> tb_blk, tb_ptr, tg_prior, tg_base;
-        for (size_t e = 0; e < targets.size(); ++e) {
-          if (e == 0 || targets[e][0] != targets[e - 1][0]) { tb_blk.push_back(targets[e][0]); tb_ptr.push_back((int)e); }
-          tg_prior.push_back(targets[e][1]);
-          tg_base.push_back(targets[e][2]);
-        }
-        tb_ptr.push_back((int)targets.size());
-        pr_pose.upload(q_pose); pr_sens.upload(q_sens); pr_po.upload(q_po); pr_so.upload(q_so); pr_pdim.upload(q_pdim);
-        pr_pos.upload(q_pos); pr_A.upload(q_A);
-        pr_tb_blk.upload(tb_blk); pr_tb_ptr.upload(tb_ptr); pr_tg_prior.upload(tg_prior); pr_tg_base.upload(tg_base);
-        pr_r.alloc(3 * (size_t)Q.n); pr_J.alloc(36 * (size_t)Q.n); pr_jx.alloc(3 * (size_t)Q.n);
-        Q.pose = pr_pose.p; Q.sens = pr_sens.p; Q.pos = pr_pos.p; Q.A = pr_A.p; Q.po = pr_po.p; Q.so = pr_so.p;
-        Q.pdim = pr_pdim.p; Q.r = pr_r.p; Q.J = pr_J.p; Q.jx = pr_jx.p;
-        Q.loss_type = p.prior_loss_type; Q.loss_scale = p.prior_loss_scale;
-        Q.n_tblk = (int)tb_blk.size();
-        Q.tb_blk = pr_tb_blk.p; Q.tb_ptr = pr_tb_ptr.p; Q.tg_prior = pr_tg_prior.p; Q.tg_base = pr_tg_base.p;
-      }
-    }
-    res_out->num_residuals = (int32_t)(2 * n_active_global) + 3 * Q.n;
-    res_out->num_effective_parameters = n_c + poff;
-    if (n_var_sensors > 0 && comm.world > 1)
+    split_linearize = dev_switch_int("COLMAP_AMD_BA_SPLIT_LINEARIZE", 1) != 0;  // read per solve: tests toggle it
+    res_out->num_residuals = (int32_t)(2 * lay.n_active_global) + 3 * lay.n_priors();
+    res_out->num_effective_parameters = lay.n_c + lay.n_p;
+    if (lay.n_var_sensors > 0 && comm.world > 1)
       throw std::runtime_error("refine_sensor_from_rig is not supported by the sharded solve");
-    if (n_active_global == 0) return 0;
-    if (n == 0)
+    if (lay.n_active_global == 0) return 0;
+    if (lay.n == 0)
       throw std::runtime_error("rank " + std::to_string(comm.rank) + " holds no observation: use fewer ranks "
                                "than images");
+    upload_layout();
+    allocate_work_buffers();
+    const int64_t n_active_global = lay.n_active_global;
+    lay.release_observation_arrays(keep_obs_maps);  // (a 20 M-observation solve does not hold them through the LM loop)
+    stage("upload+alloc");
+    // uploads / memsets above ran on the NULL stream, the solve runs on a non-blocking stream
+    BA_HIP(hipDeviceSynchronize());
+    return (int)std::min<int64_t>(n_active_global, 1 << 30);
+  }
 
-    stage("blocks+chunks");
-    // upload
-    o_pose.upload(h_o_pose); o_cam.upload(h_o_cam); o_pt.upload(h_o_pt); o_xy.upload(h_xy);
+  // The layout's arrays to the device, every view field beside its upload
+  void upload_layout() {
+    const ba_problem& p = prob;
+    const ba_layout::Layout& L = lay;
+    const bool has_sensors = L.has_sensors;
+    V.n_obs = L.n; V.n_poses = p.num_poses; V.n_cams = p.num_cams; V.n_points = p.num_points;
+    V.n_c = L.n_c; V.n_p = L.n_p; V.n_blk = L.n_blk(); V.n_chunks = (int)L.chunk_blk.size();
+    V.kd = kd;
+    V.bd = bd;
+    V.o_pose = o_pose.upload(L.o_pose); V.o_cam = o_cam.upload(L.o_cam); V.o_pt = o_pt.upload(L.o_pt);
+    V.o_xy = o_xy.upload(L.o_xy);
+    V.o_sensor = nullptr; V.sensors = nullptr; V.sens_off = nullptr;
+    V.n_sensors = has_sensors ? p.num_sensors : 0;
     if (has_sensors) {
-      o_sensor.upload(h_o_sensor);
-      sensors.upload(std::vector<double>(p.sensors, p.sensors + (size_t)7 * p.num_sensors));
+      V.o_sensor = o_sensor.upload(L.o_sensor);
+      V.sensors = sensors.upload(std::vector<double>(p.sensors, p.sensors + (size_t)7 * p.num_sensors));
       sensors2.alloc(sensors.n);
       BA_HIP(hipMemcpy(sensors2.p, sensors.p, sizeof(double) * sensors.n, hipMemcpyDeviceToDevice));
-      if (n_var_sensors > 0) sens_off.upload(h_sens_off);
+      if (L.n_var_sensors > 0) V.sens_off = sens_off.upload(L.sens_off);
     }
-    pose_off.upload(h_pose_off); pose_dim.upload(h_pose_dim); pose_fix.upload(h_pose_fix);
-    cam_off.upload(h_cam_off); cam_dim.upload(h_cam_dim); cam_var.upload(h_cam_var);
-    cam_model.upload(std::vector<int>(p.cam_model, p.cam_model + p.num_cams));
-    pt_off.upload(h_pt_off); pt_ptr.upload(h_pt_ptr);
-    blk_off.upload(h_blk_off); blk_dim.upload(h_blk_dim); blk_kind.upload(h_blk_kind); blk_moff.upload(h_blk_moff);
-    // Image sharding: (point, intrinsics block) incidences whose observations sit on more than one rank -- the
-    // pairs the local Schur-Jacobi terms cannot see (ba_inc_* kernels). Every rank walks the whole problem, so all
-    // ranks build the same list in the same order; a rank's own observations of an incidence go into a CSR list.
+    V.pose_off = pose_off.upload(L.pose_off); V.pose_dim = pose_dim.upload(L.pose_dim); V.pose_fix = pose_fix.upload(L.pose_fix);
+    V.cam_off = cam_off.upload(L.cam_off); V.cam_dim = cam_dim.upload(L.cam_dim);
+    {
+      std::vector<int> h_cam_var((size_t)p.num_cams * kd, 0);  // the tier's row stride
+      for (int k = 0; k < p.num_cams; ++k)
+        for (int d = 0; d < L.cam_nvar[k]; ++d) h_cam_var[(size_t)k * kd + d] = L.cam_var[(size_t)k * BA_CAM_STRIDE + d];
+      V.cam_var = cam_var.upload(h_cam_var);
+    }
+    V.cam_model = cam_model.upload(std::vector<int>(p.cam_model, p.cam_model + p.num_cams));
+    V.pt_off = pt_off.upload(L.pt_off); V.pt_ptr = pt_ptr.upload(L.pt_ptr);
+    V.blk_off = blk_off.upload(L.blk_off); V.blk_dim = blk_dim.upload(L.blk_dim);
+    V.blk_kind = blk_kind.upload(L.blk_kind); V.blk_moff = blk_moff.upload(L.blk_moff);
+    // position priors (ba_prior_* kernels)
+    Q = PriorView{};
+    Q.n = L.n_priors();
+    if (Q.n > 0) {
+      Q.pose = pr_pose.upload(L.pr_pose); Q.sens = pr_sens.upload(L.pr_sens);
+      Q.po = pr_po.upload(L.pr_po); Q.so = pr_so.upload(L.pr_so); Q.pdim = pr_pdim.upload(L.pr_pdim);
+      Q.pos = pr_pos.upload(L.pr_pos); Q.A = pr_A.upload(L.pr_A);
+      Q.n_tblk = (int)L.tb_blk.size();
+      Q.tb_blk = pr_tb_blk.upload(L.tb_blk); Q.tb_ptr = pr_tb_ptr.upload(L.tb_ptr);
+      Q.tg_prior = pr_tg_prior.upload(L.tg_prior); Q.tg_base = pr_tg_base.upload(L.tg_base);
+      Q.loss_type = p.prior_loss_type; Q.loss_scale = p.prior_loss_scale;
+    }
+    // image sharding: the incidences that span ranks (ba_inc_* kernels)
     IV = IncView{};
-    if (comm.world > 1 && !comm.by_point) {
-      // global pass: per (point, camera) the set of ranks that hold an observation of it
-      std::vector<std::pair<long long, int>> keys;  // (point * num_cams + cam, rank)
-      for (int64_t o = 0; o < p.num_obs; ++o) {
-        const int pi = p.obs_pose[o], ci = p.obs_cam[o], xi = p.obs_point[o];
-        const int sv = p.obs_sensor ? p.obs_sensor[o] : -1;
-        const bool sens_var = sv >= 0 && p.sensor_const != nullptr && !p.sensor_const[sv];
-        if (p.pose_const[pi] && cam_nvar[ci] == 0 && p.point_const[xi] && !sens_var) continue;  // not active
-        if (cam_nvar[ci] == 0 || p.point_const[xi]) continue;                                     // no coupling through this block
-        keys.emplace_back((long long)xi * p.num_cams + ci, pi % comm.world);
-      }
-      std::sort(keys.begin(), keys.end());
-      keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-      std::vector<long long> spanning;
-      for (size_t k = 0; k + 1 < keys.size(); ++k)
-        if (keys[k].first == keys[k + 1].first && (spanning.empty() || spanning.back() != keys[k].first))
-          spanning.push_back(keys[k].first);
-      if (!spanning.empty()) {
-        const int ni = (int)spanning.size();
-        std::vector<int> h_pt(ni), h_blk(ni), h_ptr(ni + 1, 0), h_obs;
-        // device order of the incidences: by block, then by (point, camera) key -- a block's run is contiguous, so
-        // its terms are summed in one fixed order (ba_inc_correct_kernel); `pos` = key-order index -> device index
-        std::vector<int> by_blk(ni), pos(ni);
-        std::iota(by_blk.begin(), by_blk.end(), 0);
-        std::stable_sort(by_blk.begin(), by_blk.end(), [&](int a, int b) {
-          return blk_of_cam[(int)(spanning[a] % p.num_cams)] < blk_of_cam[(int)(spanning[b] % p.num_cams)];
-        });
-        for (int i = 0; i < ni; ++i) {
-          pos[by_blk[i]] = i;
-          h_pt[i] = (int)(spanning[by_blk[i]] / p.num_cams);
-          h_blk[i] = blk_of_cam[(int)(spanning[by_blk[i]] % p.num_cams)];
-        }
-        // this rank's observations, c-order index c, by incidence
-        std::vector<std::pair<int, int>> mine;  // (incidence, c)
-        for (int c = 0; c < n; ++c) {
-          const long long key = (long long)h_o_pt[c] * p.num_cams + h_o_cam[c];
-          const auto it = std::lower_bound(spanning.begin(), spanning.end(), key);
-          if (it != spanning.end() && *it == key) mine.emplace_back(pos[(int)(it - spanning.begin())], c);
-        }
-        std::sort(mine.begin(), mine.end());
-        for (const auto& m : mine) h_ptr[m.first + 1]++;
-        for (int i = 0; i < ni; ++i) h_ptr[i + 1] += h_ptr[i];
-        h_obs.reserve(mine.size());
-        for (const auto& m : mine) h_obs.push_back(m.second);
-        if (h_obs.empty()) h_obs.push_back(0);
-        // chunks of <= kIncChunk incidences of one block, and every block's range of chunks
-        const int nblk = (int)h_blk_off.size();
-        std::vector<int> h_cblk, h_cbeg, h_bchunk(nblk + 1, 0);
-        for (int i = 0; i < ni;) {
-          int e = i;
-          while (e < ni && h_blk[e] == h_blk[i] && e - i < kIncChunk) ++e;
-          h_cblk.push_back(h_blk[i]);
-          h_cbeg.push_back(i);
-          h_bchunk[h_blk[i] + 1]++;
-          i = e;
-        }
-        h_cbeg.push_back(ni);
-        for (int b = 0; b < nblk; ++b) h_bchunk[b + 1] += h_bchunk[b];
-        inc_chunk_blk.upload(h_cblk); inc_chunk_beg.upload(h_cbeg); inc_blk_chunk.upload(h_bchunk);
-        inc_part.alloc(h_cblk.size() * (size_t)KD_WIDE * KD_WIDE);
-        IV.n_chunks = (int)h_cblk.size(); IV.chunk_blk = inc_chunk_blk.p; IV.chunk_beg = inc_chunk_beg.p;
-        IV.blk_chunk = inc_blk_chunk.p; IV.part = inc_part.p;
-        inc_pt.upload(h_pt); inc_blk.upload(h_blk); inc_ptr.upload(h_ptr); inc_obs.upload(h_obs);
-        inc_wloc.alloc((size_t)ni * KD_WIDE * 3); inc_wtot.alloc((size_t)ni * KD_WIDE * 3);
-        IV.n = ni; IV.pt = inc_pt.p; IV.blk = inc_blk.p; IV.ptr = inc_ptr.p; IV.obs = inc_obs.p;
-      }
+    if (L.inc.n() > 0) {
+      IV.n = L.inc.n();
+      IV.pt = inc_pt.upload(L.inc.pt); IV.blk = inc_blk.upload(L.inc.blk);
+      IV.ptr = inc_ptr.upload(L.inc.ptr); IV.obs = inc_obs.upload(L.inc.obs);
+      IV.n_chunks = (int)L.inc.chunk_blk.size();
+      IV.chunk_blk = inc_chunk_blk.upload(L.inc.chunk_blk); IV.chunk_beg = inc_chunk_beg.upload(L.inc.chunk_beg);
+      IV.blk_chunk = inc_blk_chunk.upload(L.inc.blk_chunk);
     }
-    // pairs of observations of one point inside one block: p-order block offsets per kind and room for the W's
-    // (ba_obs_w_kernel / ba_block_schur_cross_kernel), only for the kinds that have such pairs
+    // pairs of observations of one point inside one block: p-order block offsets per kind (ba_obs_w_kernel /
+    // ba_block_schur_cross_kernel), only for the kinds that have such pairs
     for (int kind = 0; kind < 3; ++kind) {
-      V.a_boff[kind] = nullptr; V.Wp[kind] = nullptr;
       V.wdim[kind] = kind == 1 ? kd : 6;
-      if (n_paired_kind[kind] <= 0) continue;
-      std::vector<int> h_ab(n, -1);
-      for (int a = 0; a < n; ++a) {
-        if (kind == 0) h_ab[a] = h_pose_off[h_a_pose[a]];
-        else if (kind == 1) h_ab[a] = h_cam_off[h_a_cam[a]];
-        else h_ab[a] = (has_sensors && h_a_sensor[a] >= 0) ? h_sens_off[h_a_sensor[a]] : -1;
-      }
-      a_boff[kind].upload(h_ab);
-      Wp[kind].alloc((size_t)n * V.wdim[kind] * 3);
-      V.a_boff[kind] = a_boff[kind].p; V.Wp[kind] = Wp[kind].p;
+      V.a_boff[kind] = L.n_paired_kind[kind] > 0 ? a_boff[kind].upload(L.a_boff[kind]) : nullptr;
     }
-    // single GPU: the pair incidences themselves, sorted by block (ba_pair_cross_kernel); a sharded solve keeps the
-    // per-observation kernel for its local pairs (the cross-rank ones are IV's)
+    // single GPU: the pair incidences themselves (ba_pair_cross_kernel)
     PV = IncView{};
     n_pair_blk = 0;
-    if (n_paired > 0 && comm.world == 1 && dev_switch_int("COLMAP_AMD_BA_PAIR_INCIDENCES", 1) != 0) {
-      std::vector<int> blk_of_off(std::max(off, 0) + 1, -1);  // tangent offset -> block
-      for (int b = 0; b < n_blk; ++b) blk_of_off[h_blk_off[b]] = b;
-      struct Inc { int blk, pt, first, count; };
-      std::vector<Inc> incs;
-      std::vector<int> members;  // p-order observation indices, grouped per incidence
-      std::vector<std::pair<int, int>> grp;  // (block offset, a) of one point and kind
-      for (int kind = 0; kind < 3; ++kind) {
-        if (n_paired_kind[kind] <= 0) continue;
-        std::vector<int> h_ab(n);
-        for (int a = 0; a < n; ++a) {
-          if (kind == 0) h_ab[a] = h_pose_off[h_a_pose[a]];
-          else if (kind == 1) h_ab[a] = h_cam_off[h_a_cam[a]];
-          else h_ab[a] = (has_sensors && h_a_sensor[a] >= 0) ? h_sens_off[h_a_sensor[a]] : -1;
-        }
-        for (int j = 0; j < p.num_points; ++j) {
-          if (h_pt_off[j] < 0) continue;  // a constant point has no C^-1: its observations do not couple
-          grp.clear();
-          for (int a = h_pt_ptr[j]; a < h_pt_ptr[j + 1]; ++a)
-            if (h_ab[a] >= 0) grp.emplace_back(h_ab[a], a);
-          std::sort(grp.begin(), grp.end());
-          for (size_t i = 0; i < grp.size();) {
-            size_t e = i;
-            while (e < grp.size() && grp[e].first == grp[i].first) ++e;
-            if (e - i >= 2) {
-              incs.push_back({blk_of_off[grp[i].first], j, (int)members.size(), (int)(e - i)});
-              for (size_t k = i; k < e; ++k) members.push_back(grp[k].second);
-            }
-            i = e;
-          }
-        }
-      }
-      if (!incs.empty()) {
-        std::stable_sort(incs.begin(), incs.end(), [](const Inc& a, const Inc& b) { return a.blk < b.blk; });
-        const int ni = (int)incs.size();
-        std::vector<int> h_pt(ni), h_blk(ni), h_ptr(ni + 1, 0), h_mem;
-        h_mem.reserve(members.size());
-        for (int i = 0; i < ni; ++i) {
-          h_pt[i] = incs[i].pt; h_blk[i] = incs[i].blk;
-          h_mem.insert(h_mem.end(), members.begin() + incs[i].first, members.begin() + incs[i].first + incs[i].count);
-          h_ptr[i + 1] = (int)h_mem.size();
-        }
-        std::vector<int> h_cblk, h_cbeg, h_bchunk(n_blk + 1, 0), h_pblk;
-        for (int i = 0; i < ni;) {
-          int e = i;
-          while (e < ni && h_blk[e] == h_blk[i] && e - i < kPairChunk) ++e;
-          if (h_pblk.empty() || h_pblk.back() != h_blk[i]) h_pblk.push_back(h_blk[i]);
-          h_cblk.push_back(h_blk[i]); h_cbeg.push_back(i);
-          h_bchunk[h_blk[i] + 1]++;
-          i = e;
-        }
-        h_cbeg.push_back(ni);
-        for (int b = 0; b < n_blk; ++b) h_bchunk[b + 1] += h_bchunk[b];
-        pv_pt.upload(h_pt); pv_blk.upload(h_blk); pv_ptr.upload(h_ptr); pv_mem.upload(h_mem);
-        pv_chunk_blk.upload(h_cblk); pv_chunk_beg.upload(h_cbeg); pv_blk_chunk.upload(h_bchunk); pv_pair_blk.upload(h_pblk);
-        pv_part.alloc(h_cblk.size() * (size_t)KD_WIDE * KD_WIDE);
-        PV.n = ni; PV.pt = pv_pt.p; PV.blk = pv_blk.p; PV.ptr = pv_ptr.p; PV.obs = pv_mem.p;
-        PV.n_chunks = (int)h_cblk.size(); PV.chunk_blk = pv_chunk_blk.p; PV.chunk_beg = pv_chunk_beg.p;
-        PV.blk_chunk = pv_blk_chunk.p; PV.part = pv_part.p;
-        n_pair_blk = (int)h_pblk.size();
-      }
+    if (L.pairs.n() > 0) {
+      PV.n = L.pairs.n();
+      PV.pt = pv_pt.upload(L.pairs.pt); PV.blk = pv_blk.upload(L.pairs.blk);
+      PV.ptr = pv_ptr.upload(L.pairs.ptr); PV.obs = pv_mem.upload(L.pairs.obs);
+      PV.n_chunks = (int)L.pairs.chunk_blk.size();
+      PV.chunk_blk = pv_chunk_blk.upload(L.pairs.chunk_blk); PV.chunk_beg = pv_chunk_beg.upload(L.pairs.chunk_beg);
+      PV.blk_chunk = pv_blk_chunk.upload(L.pairs.blk_chunk);
+      pv_pair_blk.upload(L.pairs.blocks);
+      n_pair_blk = (int)L.pairs.blocks.size();
     }
-    chunk_blk.upload(h_chunk_blk); chunk_beg.upload(h_chunk_beg); chunk_end.upload(h_chunk_end);
-    c2a.upload(h_c2a); a2c.upload(h_a2c); solo.upload(h_solo); tile_pt.upload(h_tile_pt);
+    V.chunk_blk = chunk_blk.upload(L.chunk_blk); V.chunk_beg = chunk_beg.upload(L.chunk_beg);
+    V.chunk_end = chunk_end.upload(L.chunk_end);
+    V.c2a = c2a.upload(L.c2a); V.a2c = a2c.upload(L.a2c); V.solo = solo.upload(L.solo);
+    V.tile_pt = tile_pt.upload(L.tile_pt);
+    V.n_tiles = (int)L.tile_pt.size() - 1;
     {
-      std::vector<int4> h_tile_info(std::max<size_t>(h_tile_pt.size(), 2) - 1, make_int4(0, 0, 0, 0));
-      for (size_t t = 0; t + 1 < h_tile_pt.size(); ++t) {
-        const int q0 = h_tile_pt[t], q1 = h_tile_pt[t + 1];
-        h_tile_info[t] = make_int4(q0, q1, h_pt_ptr[q0], h_pt_ptr[q1] - h_pt_ptr[q0]);
+      std::vector<int4> h_tile_info(std::max<size_t>(L.tile_pt.size(), 2) - 1, make_int4(0, 0, 0, 0));
+      for (size_t t = 0; t + 1 < L.tile_pt.size(); ++t) {
+        const int q0 = L.tile_pt[t], q1 = L.tile_pt[t + 1];
+        h_tile_info[t] = make_int4(q0, q1, L.pt_ptr[q0], L.pt_ptr[q1] - L.pt_ptr[q0]);
       }
-      tile_info.upload(h_tile_info);
+      V.tile_info = tile_info.upload(h_tile_info);
     }
-    a_pose.upload(h_a_pose); a_cam.upload(h_a_cam); a_pt.upload(h_a_pt); a_xy.upload(h_a_xy);
-    if (has_sensors) a_sensor.upload(h_a_sensor);
-    V.a_pose = a_pose.p; V.a_cam = a_cam.p; V.a_pt = a_pt.p; V.a_xy = a_xy.p;
-    V.a_sensor = has_sensors ? a_sensor.p : nullptr;
-    V.n_tiles = (int)h_tile_pt.size() - 1;
-    blk_chunk_ptr.upload(h_blk_chunk_ptr);
-    blk_fin_end.upload(h_blk_fin_end);
-    n_heavy = (int)h_heavy.size();
-    if (h_heavy.empty()) h_heavy.push_back(0);
-    heavy_blk.upload(h_heavy);
-    cpart.alloc((size_t)h_chunk_blk.size() * bd * bd);
-    poses.upload(std::vector<double>(p.poses, p.poses + 7 * (size_t)p.num_poses));
-    cams.upload(std::vector<double>(p.cams, p.cams + BA_CAM_STRIDE * (size_t)p.num_cams));
-    points.upload(std::vector<double>(p.points, p.points + 3 * (size_t)p.num_points));
-    poses2.alloc(poses.n); cams2.alloc(cams.n); points2.alloc(points.n);
+    // (the explicit Schur formation reads the p-order topology too, whatever the linearisation does)
+    V.a_pose = a_pose.upload(L.a_pose); V.a_cam = a_cam.upload(L.a_cam); V.a_pt = a_pt.upload(L.a_pt);
+    V.a_xy = a_xy.upload(L.a_xy);
+    V.a_sensor = has_sensors ? a_sensor.upload(L.a_sensor) : nullptr;
+    V.blk_chunk_ptr = blk_chunk_ptr.upload(L.blk_chunk_ptr);
+    V.blk_fin_end = blk_fin_end.upload(L.blk_fin_end);
+    V.n_heavy = n_heavy = (int)L.heavy.size();
+    V.heavy_blk = heavy_blk.upload(L.heavy.empty() ? std::vector<int>(1, 0) : L.heavy);
+    V.poses = poses.upload(std::vector<double>(p.poses, p.poses + 7 * (size_t)p.num_poses));
+    V.cams = cams.upload(std::vector<double>(p.cams, p.cams + BA_CAM_STRIDE * (size_t)p.num_cams));
+    V.points = points.upload(std::vector<double>(p.points, p.points + 3 * (size_t)p.num_points));
+  }
+
+  // Everything the solve writes: Jacobian planes, per-chunk partials, the vectors of the LM / PCG loops
+  void allocate_work_buffers() {
+    const ba_problem& p = prob;
+    const ba_layout::Layout& L = lay;
+    const int n = L.n, n_c = L.n_c, poff = L.n_p, n_blk = L.n_blk();
     const size_t N = (size_t)n;
+    if (Q.n > 0) {
+      pr_r.alloc(3 * (size_t)Q.n); pr_J.alloc(36 * (size_t)Q.n); pr_jx.alloc(3 * (size_t)Q.n);
+      Q.r = pr_r.p; Q.J = pr_J.p; Q.jx = pr_jx.p;
+    }
+    if (IV.n > 0) {
+      inc_part.alloc((size_t)IV.n_chunks * KD_WIDE * KD_WIDE);
+      IV.part = inc_part.p;
+      inc_wloc.alloc((size_t)IV.n * KD_WIDE * 3); inc_wtot.alloc((size_t)IV.n * KD_WIDE * 3);
+    }
+    for (int kind = 0; kind < 3; ++kind) {  // room for the W's of the kinds with pairs
+      V.Wp[kind] = nullptr;
+      if (L.n_paired_kind[kind] <= 0) continue;
+      Wp[kind].alloc(N * V.wdim[kind] * 3);
+      V.Wp[kind] = Wp[kind].p;
+    }
+    if (PV.n > 0) {
+      pv_part.alloc((size_t)PV.n_chunks * KD_WIDE * KD_WIDE);
+      PV.part = pv_part.p;
+    }
+    cpart.alloc((size_t)V.n_chunks * bd * bd);
+    poses2.alloc(poses.n); cams2.alloc(cams.n); points2.alloc(points.n);
     Jpose.alloc(2 * PD * N); Jcam.alloc(2 * (size_t)kd * N); Jpt.alloc(6 * N); res.alloc(2 * N); res_p.alloc(2 * N);
     jx.alloc(2 * N); v.alloc(2 * N); Gobs.alloc(4 * N);
-    if (n_var_sensors > 0) Jsens.alloc(12 * N);
+    if (L.n_var_sensors > 0) Jsens.alloc(12 * N);
+    V.Jsens = L.n_var_sensors > 0 ? Jsens.p : nullptr;
     {
-      op32 = opt.operator_precision == BA_OPERATOR_F32 && n_var_sensors == 0 && V.n_tiles > 0 && comm.world == 1;
+      op32 = opt.operator_precision == BA_OPERATOR_F32 && L.n_var_sensors == 0 && V.n_tiles > 0 && comm.world == 1;
       if (op32) { Jpose32.alloc(2 * PD * N); Jcam32.alloc(2 * (size_t)kd * N); Jpt32.alloc(6 * N); }
       V.Jpose32 = op32 ? Jpose32.p : nullptr;
       V.Jcam32 = op32 ? Jcam32.p : nullptr;
@@ -3740,7 +3368,7 @@ struct Solver {
     }
     {
       plain_model = -1;
-      const bool plain_ok = dev_switch_int("COLMAP_AMD_BA_PLAIN_LINEARIZE", 1) != 0 && !op32 && !has_sensors &&
+      const bool plain_ok = dev_switch_int("COLMAP_AMD_BA_PLAIN_LINEARIZE", 1) != 0 && !op32 && !L.has_sensors &&
                             opt.loss_type == BA_LOSS_TRIVIAL && p.num_cams > 0;
       if (plain_ok) {
         const int m0 = p.cam_model[0];
@@ -3759,44 +3387,21 @@ struct Solver {
     scale_c.alloc(n_c); scale_p.alloc(poff);
     Dc.alloc(n_c); Dp.alloc(poff); rhs.alloc(n_c); x.alloc(n_c); r.alloc(n_c); z.alloc(n_c); pdir.alloc(n_c);
     q.alloc(n_c); dp.alloc(poff); stepc.alloc(n_c); stepp.alloc(poff);
-    Cinv.alloc(9 * (size_t)p.num_points); M.alloc(moff); Minv.alloc(moff);
+    Cinv.alloc(9 * (size_t)p.num_points); M.alloc(L.moff_total); Minv.alloc(L.moff_total);
     tbuf.alloc(poff); tmpc.alloc(n_c);
     scalars.alloc(NSCALAR);
     pcg_part.alloc((size_t)grid_for(n_blk, 256) + 1);
     partials.alloc((size_t)std::max(grid_for(n, 256), std::max(p.num_points, 1)) + 1);  // one slot per linearise workgroup / point tile
-
-    V.n_obs = n; V.n_poses = p.num_poses; V.n_cams = p.num_cams; V.n_points = p.num_points;
-    V.n_c = n_c; V.n_p = poff; V.n_blk = n_blk; V.n_chunks = (int)h_chunk_blk.size();
-    V.poses = poses.p; V.cams = cams.p; V.points = points.p;
-    V.o_pose = o_pose.p; V.o_cam = o_cam.p; V.o_pt = o_pt.p; V.o_xy = o_xy.p;
-    V.kd = kd;
-    V.bd = bd;
-    V.o_sensor = has_sensors ? o_sensor.p : nullptr;
-    V.sensors = has_sensors ? sensors.p : nullptr;
-    V.sens_off = n_var_sensors > 0 ? sens_off.p : nullptr;
-    V.Jsens = n_var_sensors > 0 ? Jsens.p : nullptr;
-    V.n_sensors = has_sensors ? p.num_sensors : 0;
     if (opt.loss_type < BA_LOSS_TRIVIAL || opt.loss_type > BA_LOSS_HUBER)
       throw std::runtime_error("unknown loss_type " + std::to_string(opt.loss_type));
     if (opt.loss_type != BA_LOSS_TRIVIAL && !(opt.loss_scale > 0.0))
       throw std::runtime_error("loss_scale must be positive");
     V.loss_type = opt.loss_type;
     V.loss_scale = opt.loss_scale;
-    V.pose_off = pose_off.p; V.pose_dim = pose_dim.p; V.pose_fix = pose_fix.p;
-    V.cam_off = cam_off.p; V.cam_dim = cam_dim.p; V.cam_var = cam_var.p; V.cam_model = cam_model.p;
-    V.pt_off = pt_off.p; V.pt_ptr = pt_ptr.p;
-    V.blk_off = blk_off.p; V.blk_dim = blk_dim.p; V.blk_kind = blk_kind.p; V.blk_moff = blk_moff.p;
-    V.chunk_blk = chunk_blk.p; V.chunk_beg = chunk_beg.p; V.chunk_end = chunk_end.p;
-    V.c2a = c2a.p; V.a2c = a2c.p; V.solo = solo.p; V.tile_pt = tile_pt.p; V.tile_info = tile_info.p;
-    V.blk_chunk_ptr = blk_chunk_ptr.p; V.cpart = cpart.p;
-    V.blk_fin_end = blk_fin_end.p; V.heavy_blk = heavy_blk.p; V.n_heavy = n_heavy;
+    V.cpart = cpart.p;
     V.Jpose = Jpose.p; V.Jcam = Jcam.p; V.Jpt = Jpt.p; V.res = res.p; V.res_p = res_p.p;
     V.scale_c = scale_c.p; V.scale_p = scale_p.p; V.scalars = scalars.p;
     maxbuf.alloc(std::max(comm.world, 1));
-    stage("upload+alloc");
-    // uploads / memsets above ran on the NULL stream, the solve runs on a non-blocking stream
-    BA_HIP(hipDeviceSynchronize());
-    return (int)std::min<int64_t>(n_active_global, 1 << 30);
   }
 
   void launch_linearize(bool jac, const double* P, const double* Cm, const double* X, const double* Sn, int slot) {
@@ -4179,7 +3784,7 @@ struct Solver {
   // Minv = the inverted blocks of the Schur-Jacobi preconditioner. Returns whether its matrix-core kernel ran, between
   // ev2 and ev3 (the caller adds their interval to g_mfma_ms after its next synchronisation)
   bool form_preconditioner() {
-    if (V.n_chunks == 0) BA_HIP(hipMemsetAsync(M.p, 0, sizeof(double) * std::max(moff_total, 1), st));
+    if (V.n_chunks == 0) BA_HIP(hipMemsetAsync(M.p, 0, sizeof(double) * std::max(lay.moff_total, 1), st));
     if (V.n_chunks > 0) {  // (ba_block_mat_finalize_kernel<false> assigns every entry of every block)
       if (rhs_pass_fused())
         BA_LAUNCH((ba_point_pass_tiled_kernel<4>), dim3(V.n_tiles), dim3(TILE_PTS), st, V, Cinv.p, jx.p, gp.p, v.p, dp.p, (double*)nullptr, Gobs.p);
@@ -4192,7 +3797,7 @@ struct Solver {
       BA_HIP(hipEventRecord(ev3, st));
       heavy_reduce(bd * bd);
       BA_LAUNCH(ba_block_mat_finalize_kernel<false>, dim3(grid_for(V.n_blk * bd * bd, 128)), dim3(128), st, V, M.p);
-      if (n_paired > 0) {  // observation pairs of a point inside one block: shared intrinsics, rig frames
+      if (lay.n_paired > 0) {  // observation pairs of a point inside one block: shared intrinsics, rig frames
         with_tier([&](auto t) {
           BA_LAUNCH(ba_obs_w_kernel<t.bd>, dim3(grid_for(V.n_obs, 256)), dim3(256), st, V);
           if (PV.n > 0) {  // per incidence (single GPU)
@@ -4219,7 +3824,7 @@ struct Solver {
         BA_LAUNCH(ba_inc_finalize_kernel<t.kdt>, dim3(grid_for((size_t)V.n_blk * t.kdt * t.kdt, 256)), dim3(256), st, V, IV, M.p);
       });
     }
-    comm.allreduce(M.p, (size_t)moff_total, st);
+    comm.allreduce(M.p, (size_t)lay.moff_total, st);
     with_tier([&](auto t) {
       BA_LAUNCH(ba_block_invert_kernel<t.bd>, dim3(grid_for(V.n_blk, 64)), dim3(64), st, V, Dc.p, M.p, Minv.p);
     });
@@ -4287,16 +3892,16 @@ struct Solver {
       std::vector<double> hs(sensors.n);
       BA_HIP(hipMemcpyAsync(hs.data(), sensors.p, sizeof(double) * sensors.n, hipMemcpyDeviceToHost, st));
       BA_HIP(hipStreamSynchronize(st));
-      copy_variable(prob.sensors, hs, h_sens_off, prob.num_sensors, 7);
+      copy_variable(prob.sensors, hs, lay.sens_off, prob.num_sensors, 7);
     }
     std::vector<double> hp(poses.n), hc(cams.n), hx(points.n);
     BA_HIP(hipMemcpyAsync(hp.data(), poses.p, sizeof(double) * poses.n, hipMemcpyDeviceToHost, st));
     BA_HIP(hipMemcpyAsync(hc.data(), cams.p, sizeof(double) * cams.n, hipMemcpyDeviceToHost, st));
     BA_HIP(hipMemcpyAsync(hx.data(), points.p, sizeof(double) * points.n, hipMemcpyDeviceToHost, st));
     BA_HIP(hipStreamSynchronize(st));
-    copy_variable(prob.poses, hp, h_pose_off, prob.num_poses, 7);
-    copy_variable(prob.cams, hc, h_cam_off, prob.num_cams, BA_CAM_STRIDE);
-    copy_variable(prob.points, hx, h_pt_off, prob.num_points, 3);
+    copy_variable(prob.poses, hp, lay.pose_off, prob.num_poses, 7);
+    copy_variable(prob.cams, hc, lay.cam_off, prob.num_cams, BA_CAM_STRIDE);
+    copy_variable(prob.points, hx, lay.pt_off, prob.num_points, 3);
   }
 
   void run(ba_result* out) {
@@ -4568,26 +4173,24 @@ int Solver::estimate_covariance(const ba_covariance_options& co, CovHandle& h) {
   if (co.params != BA_COV_POSES) {
     BA_HIP(hipMemcpyAsync(h.point_cov.data(), pcov.p, sizeof(double) * h.point_cov.size(), hipMemcpyDeviceToHost, st));
     BA_HIP(hipStreamSynchronize(st));
-    for (int j = 0; j < p.num_points; ++j) h.point_has[j] = h_pt_off[j] >= 0;
+    for (int j = 0; j < p.num_points; ++j) h.point_has[j] = lay.pt_off[j] >= 0;
   }
   if (co.params == BA_COV_POINTS || nc == 0) return BA_COV_OK;
   // 2. the camera-side order of the covariance system: others (intrinsics, then sensor_from_rig blocks, in the solver's
   // order) padded with identity rows to a multiple of 64, then the poses
-  std::vector<int> pdim(p.num_poses, 0), cdim(p.num_cams, 0);
-  BA_HIP(hipMemcpy(pdim.data(), pose_dim.p, sizeof(int) * pdim.size(), hipMemcpyDeviceToHost));
-  BA_HIP(hipMemcpy(cdim.data(), cam_dim.p, sizeof(int) * cdim.size(), hipMemcpyDeviceToHost));
+  const std::vector<int>&pdim = lay.pose_dim, &cdim = lay.cam_dim;
   int n_pd = 0;
-  for (int i = 0; i < p.num_poses; ++i) n_pd += h_pose_off[i] >= 0 ? pdim[i] : 0;
+  for (int i = 0; i < p.num_poses; ++i) n_pd += lay.pose_off[i] >= 0 ? pdim[i] : 0;
   const int n_o = nc - n_pd;  // the solver's layout: poses [0, n_pd), then intrinsics and sensors
   const int n_op = (n_o + 63) / 64 * 64;
   const int n = n_op + n_pd;
   if (n > 32768)
     throw std::runtime_error("covariance: camera-side dimension " + std::to_string(n) + " exceeds the limit of 32768");
   auto remap = [&](int off) { return off < 0 ? -1 : (off < n_pd ? off + n_op : off - n_pd); };
-  std::vector<int> npose(p.num_poses), ncam(p.num_cams), nsens(h_sens_off.size());
-  for (int i = 0; i < p.num_poses; ++i) npose[i] = remap(h_pose_off[i]);
-  for (int k = 0; k < p.num_cams; ++k) ncam[k] = remap(h_cam_off[k]);
-  for (size_t k = 0; k < nsens.size(); ++k) nsens[k] = remap(h_sens_off[k]);
+  std::vector<int> npose(p.num_poses), ncam(p.num_cams), nsens(lay.sens_off.size());
+  for (int i = 0; i < p.num_poses; ++i) npose[i] = remap(lay.pose_off[i]);
+  for (int k = 0; k < p.num_cams; ++k) ncam[k] = remap(lay.cam_off[k]);
+  for (size_t k = 0; k < nsens.size(); ++k) nsens[k] = remap(lay.sens_off[k]);
   std::vector<double> sc_old(std::max(nc, 1)), sc(n, 1.0);
   BA_HIP(hipMemcpyAsync(sc_old.data(), scale_c.p, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
   BA_HIP(hipStreamSynchronize(st));
@@ -4599,9 +4202,7 @@ int Solver::estimate_covariance(const ba_covariance_options& co, CovHandle& h) {
   BA_HIP(hipMemcpy(h.scale, sc.data(), sizeof(double) * n, hipMemcpyHostToDevice));
   if (use_priors()) {
     std::vector<int> po(Q.n), so(Q.n);
-    BA_HIP(hipMemcpy(po.data(), Q.po, sizeof(int) * Q.n, hipMemcpyDeviceToHost));
-    BA_HIP(hipMemcpy(so.data(), Q.so, sizeof(int) * Q.n, hipMemcpyDeviceToHost));
-    for (int k = 0; k < Q.n; ++k) { po[k] = remap(po[k]); so[k] = remap(so[k]); }
+    for (int k = 0; k < Q.n; ++k) { po[k] = remap(lay.pr_po[k]); so[k] = remap(lay.pr_so[k]); }
     d_po.upload(po); d_so.upload(so);
   }
   prepare_exact(n);
@@ -4763,20 +4364,15 @@ int ba_solve_sharded(ba_problem* problem, const ba_options* options, int32_t gpu
 
 static int64_t ShardNumObservations(const ba_problem* p, int32_t rank, int32_t world_size, bool by_point) {
   if (!p || world_size < 1 || rank < 0 || rank >= world_size) return -1;
-  std::vector<char> cam_var(p->num_cams, 0);
+  std::vector<int> cam_nvar(p->num_cams, 0);
   for (int k = 0; k < p->num_cams; ++k) {
     const int P = num_params_of(p->cam_model[k]);
     for (int j = 0; j < P; ++j)
-      if (!p->cam_const[(size_t)k * BA_CAM_STRIDE + j]) cam_var[k] = 1;
+      if (!p->cam_const[(size_t)k * BA_CAM_STRIDE + j]) ++cam_nvar[k];
   }
   int64_t n = 0;
-  for (int64_t o = 0; o < p->num_obs; ++o) {
-    const int pi = p->obs_pose[o], xi = p->obs_point[o];
-    const int si = p->obs_sensor ? p->obs_sensor[o] : -1;
-    const bool sens_var = si >= 0 && p->sensor_const && !p->sensor_const[si];
-    if (p->pose_const[pi] && !cam_var[p->obs_cam[o]] && p->point_const[xi] && !sens_var) continue;
-    if ((by_point ? xi : pi) % world_size == rank) ++n;
-  }
+  for (int64_t o = 0; o < p->num_obs; ++o)
+    if (ba_layout::is_active(*p, cam_nvar.data(), o) && (by_point ? p->obs_point[o] : p->obs_pose[o]) % world_size == rank) ++n;
   return n;
 }
 
@@ -4982,14 +4578,14 @@ void probe_point_vector(Solver& s, const double* dev, double* out) {
   if (!out || s.V.n_p <= 0) return;
   const std::vector<double> h = probe_fetch(s, dev, (size_t)s.V.n_p);
   for (int j = 0; j < s.prob.num_points; ++j)
-    if (s.h_pt_off[j] >= 0)
-      for (int c = 0; c < 3; ++c) out[3 * (size_t)j + c] = h[(size_t)s.h_pt_off[j] + c];
+    if (s.lay.pt_off[j] >= 0)
+      for (int c = 0; c < 3; ++c) out[3 * (size_t)j + c] = h[(size_t)s.lay.pt_off[j] + c];
 }
 
 void probe_blocks(Solver& s, const double* dev, double* out, int cap) {
-  if (!out || s.moff_total <= 0) return;
-  if (s.moff_total > cap) throw std::runtime_error("ba_probe: block_cap too small");
-  const std::vector<double> h = probe_fetch(s, dev, (size_t)s.moff_total);
+  if (!out || s.lay.moff_total <= 0) return;
+  if (s.lay.moff_total > cap) throw std::runtime_error("ba_probe: block_cap too small");
+  const std::vector<double> h = probe_fetch(s, dev, (size_t)s.lay.moff_total);
   std::memcpy(out, h.data(), sizeof(double) * h.size());
 }
 
@@ -5025,6 +4621,7 @@ void probe_run(const ba_problem& p_in, const ba_options& opt, ba_probe_io& io) {
   ba_result res{};
   io.pcg_iterations = 0; io.pcg_pipelined = -1;
   io.cost = io.s_model = io.s_newcost = 0.0;
+  s.keep_obs_maps = true;  // obs_of_a and a2c outlive build()
   const int built = s.build(&res);
   io.n_active = built;
   if (io.obs_active) std::memset(io.obs_active, 0, (size_t)p.num_obs);
@@ -5036,36 +4633,19 @@ void probe_run(const ba_problem& p_in, const ba_options& opt, ba_probe_io& io) {
   const int n = V.n_obs, n_c = V.n_c;
   if (n_c > io.vec_stride) throw std::runtime_error("ba_probe: vec_stride too small");
   // ---- path facts
-  io.n_c = n_c; io.n_p = V.n_p; io.moff_total = s.moff_total;
+  io.n_c = n_c; io.n_p = V.n_p; io.moff_total = s.lay.moff_total;
   io.width_tier = s.width_tier; io.kd = s.kd; io.bd = s.bd; io.plain_model = s.plain_model;
   io.split_linearize = s.split_linearize ? 1 : 0; io.op32 = s.op32 ? 1 : 0;
   io.n_tiles = V.n_tiles; io.n_chunks = V.n_chunks; io.n_heavy = s.n_heavy; io.pv_n = s.PV.n;
-  io.rhs_pass_fused = s.rhs_pass_fused() ? 1 : 0; io.n_priors = s.Q.n; io.n_paired = s.n_paired;
-  // ---- maps
+  io.rhs_pass_fused = s.rhs_pass_fused() ? 1 : 0; io.n_priors = s.Q.n; io.n_paired = s.lay.n_paired;
+  // ---- maps: the layout's own (host) maps; of the device only its p-order topology is fetched, to check the
+  // p-order slot -> caller observation map against it below instead of trusting it
+  const ba_layout::Layout& L = s.lay;
   const std::vector<int> a_pose = probe_fetch(s, V.a_pose, (size_t)n), a_cam = probe_fetch(s, V.a_cam, (size_t)n),
-                         a_pt = probe_fetch(s, V.a_pt, (size_t)n), a2c = probe_fetch(s, V.a2c, (size_t)n),
-                         pose_dim = probe_fetch(s, V.pose_dim, (size_t)p.num_poses),
-                         cam_dim = probe_fetch(s, V.cam_dim, (size_t)p.num_cams),
-                         blk_off = probe_fetch(s, V.blk_off, (size_t)V.n_blk),
-                         blk_moff = probe_fetch(s, V.blk_moff, (size_t)V.n_blk);
+                         a_pt = probe_fetch(s, V.a_pt, (size_t)n);
   const std::vector<double> a_xy = probe_fetch(s, V.a_xy, 2 * (size_t)n);
-  // p-order slot -> caller observation: the active observations, stably sorted by point (build()). Checked against
-  // the device's own p-order topology below instead of trusted.
-  std::vector<int64_t> o_of_a;
-  {
-    std::vector<std::vector<int64_t>> by_point((size_t)p.num_points);
-    std::vector<char> cam_variable((size_t)p.num_cams, 0);
-    for (int k = 0; k < p.num_cams; ++k)
-      for (int j = 0; j < num_params_of(p.cam_model[k]); ++j)
-        if (!p.cam_const[(size_t)k * BA_CAM_STRIDE + j]) cam_variable[k] = 1;
-    for (int64_t o = 0; o < p.num_obs; ++o) {
-      const int sv = p.obs_sensor ? p.obs_sensor[o] : -1;
-      const bool sens_var = sv >= 0 && p.sensor_const != nullptr && !p.sensor_const[sv];
-      if (p.pose_const[p.obs_pose[o]] && !cam_variable[p.obs_cam[o]] && p.point_const[p.obs_point[o]] && !sens_var) continue;
-      by_point[(size_t)p.obs_point[o]].push_back(o);
-    }
-    for (const auto& l : by_point) o_of_a.insert(o_of_a.end(), l.begin(), l.end());
-  }
+  const std::vector<int64_t>& o_of_a = L.obs_of_a;
+  const std::vector<int>& a2c = L.a2c;
   if ((int)o_of_a.size() != n) throw std::runtime_error("ba_probe: active observation count");
   for (int a = 0; a < n; ++a) {
     const int64_t o = o_of_a[a];
@@ -5074,31 +4654,27 @@ void probe_run(const ba_problem& p_in, const ba_options& opt, ba_probe_io& io) {
       throw std::runtime_error("ba_probe: p-order observation map");
     if (io.obs_active) io.obs_active[o] = 1;
   }
-  auto moff_of = [&](int off) {
-    for (int b = 0; b < V.n_blk; ++b)
-      if (blk_off[b] == off) return blk_moff[b];
-    return -1;
-  };
+  auto moff_of = [&](int blk) { return blk >= 0 ? L.blk_moff[blk] : -1; };
   for (int i = 0; i < p.num_poses; ++i) {
-    const int off = s.h_pose_off[i];
+    const int off = L.pose_off[i];
     if (io.pose_off) io.pose_off[i] = off;
-    if (io.pose_dim) io.pose_dim[i] = off >= 0 ? pose_dim[i] : -1;
-    if (io.pose_moff) io.pose_moff[i] = off >= 0 ? moff_of(off) : -1;
+    if (io.pose_dim) io.pose_dim[i] = off >= 0 ? L.pose_dim[i] : -1;
+    if (io.pose_moff) io.pose_moff[i] = moff_of(L.blk_of_pose[i]);
   }
   for (int k = 0; k < p.num_cams; ++k) {
-    const int off = s.h_cam_off[k];
+    const int off = L.cam_off[k];
     if (io.cam_off) io.cam_off[k] = off;
-    if (io.cam_dim) io.cam_dim[k] = off >= 0 ? cam_dim[k] : -1;
-    if (io.cam_moff) io.cam_moff[k] = off >= 0 ? moff_of(off) : -1;
+    if (io.cam_dim) io.cam_dim[k] = off >= 0 ? L.cam_dim[k] : -1;
+    if (io.cam_moff) io.cam_moff[k] = moff_of(L.blk_of_cam[k]);
   }
   for (int k = 0; k < p.num_sensors; ++k) {
-    const int off = s.h_sens_off[k];
+    const int off = L.sens_off[k];
     if (io.sens_off) io.sens_off[k] = off;
     if (io.sens_dim) io.sens_dim[k] = off >= 0 ? 6 : -1;
-    if (io.sens_moff) io.sens_moff[k] = off >= 0 ? moff_of(off) : -1;
+    if (io.sens_moff) io.sens_moff[k] = moff_of(L.blk_of_sens[k]);
   }
   if (io.pt_off)
-    for (int j = 0; j < p.num_points; ++j) io.pt_off[j] = s.h_pt_off[j];
+    for (int j = 0; j < p.num_points; ++j) io.pt_off[j] = L.pt_off[j];
 
   // ---- 1. linearisation
   s.set_scales(0);
@@ -5129,7 +4705,7 @@ void probe_run(const ba_problem& p_in, const ba_options& opt, ba_probe_io& io) {
   if (io.Cinv) {
     const std::vector<double> h = probe_fetch(s, s.Cinv.p, 9 * (size_t)p.num_points);
     for (int j = 0; j < p.num_points; ++j)
-      if (s.h_pt_off[j] >= 0) std::memcpy(io.Cinv + 9 * (size_t)j, h.data() + 9 * (size_t)j, 9 * sizeof(double));
+      if (s.lay.pt_off[j] >= 0) std::memcpy(io.Cinv + 9 * (size_t)j, h.data() + 9 * (size_t)j, 9 * sizeof(double));
   }
   if (n_c > 0) {
     s.form_preconditioner();
