@@ -44,6 +44,11 @@
 // cache line per pixel instead of three slices), the bitmaps, one 8-byte word per depth-map pixel, all
 // indexed by a 64-bit global pixel offset; per wave a record buffer (pixel, image | in-box) of the turns of
 // the pass, a list of its walks, nine float columns for the medians, and the overflow of its stack.
+//
+// The host side: fusion_plan.h (no HIP) checks the input and holds the arithmetic -- fusion order, descriptors, the
+// pool schedule of an image (stripes, T, G, L, ticks), the limits of a walk, the window of a pass and how it halves
+// and doubles, the per-thread concatenation. Here, Workspace owns the device buffers and the Params that point at
+// them, and Run is the sequence plan -> set-up -> per image (passes, compact, read back) -> concatenate.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -57,10 +62,11 @@
 #include <string>
 #include <vector>
 
-#include "../../include/colmap_amd_fusion.h"
+#include "fusion_plan.h"
 #include "switches.h"
 
 using colmap_amd::dev_switch_int;
+using namespace fusion_plan;  // Fail, FU_CHECK, the constants shared with the host plan, DevImage
 
 #define FUSION_API __attribute__((visibility("default")))
 
@@ -70,27 +76,12 @@ namespace {
 
 thread_local std::string g_error;
 
-struct Fail : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-#define FU_CHECK(cond, msg)                                         \
-  do {                                                              \
-    if (!(cond)) throw Fail(std::string("Check failed: ") + (msg)); \
-  } while (0)
-
 #define FU_HIP(expr)                                                                        \
   do {                                                                                      \
     hipError_t e_ = (expr);                                                                 \
     if (e_ != hipSuccess) throw Fail(std::string(#expr) + ": " + hipGetErrorString(e_));    \
   } while (0)
 
-// Pixels one walk can record: max_num_pixels itself between 1 024 and 16 384 (the reference's default 10 000 is NOT
-// clamped), smaller options keep 1 024, larger ones are clamped to 16 384. oracle/fusion_oracle.cpp mirrors it.
-constexpr int kElemCapMin = 1024, kElemCapMax = 16384;
-inline int record_capacity(int max_num_pixels) { return std::min(std::max(max_num_pixels, kElemCapMin), kElemCapMax); }
-constexpr int kRowStride = 10;        // rows of a pool task (fusion.cc:250-254)
-constexpr int kWave = 64;
 // The four capacities below only decide WHERE the data of a walk lives and when a pass is cut, never the result.
 // tests/hip_emul builds this file a second time with tiny values (-DFUSION_RECORD_BUF=... etc.) so that the overflow
 // paths (record buffer full, stack spill, spill growth, radix-select medians) run on inputs of a few thousand pixels.
@@ -107,24 +98,11 @@ constexpr int kWave = 64;
 #define FUSION_MEDIAN_STAGE 2048
 #endif
 constexpr int kRecordBuf = FUSION_RECORD_BUF;   // recorded pixels of one wave in one pass (>= the record capacity of a walk: a pass's first turn always fits)
-constexpr int kWindowFirst = 256, kWindowMin = 16, kWindowMax = 32768;  // ticks of a pass: doubled after a pass without a cut, halved after a cut (8192 -> 32768: 0.695 -> 0.667 s at 8 x 2560 x 1920)
 constexpr int kStackLds = FUSION_STACK_LDS;     // stack entries of a walk held in LDS (16 B each); the rest spills to HBM
 constexpr int kStackSpill = FUSION_STACK_SPILL; // ... first size of that spill per wave (grown by the host when a walk overflows it)
 constexpr int kCommitWaves = 16;      // waves per pool thread in the commit kernel (a border stripe has ten times the walks of an inner one: 4 -> 16 waves, 0.78 -> 0.70 s at 8 x 2560 x 1920)
-constexpr int kTableBytes = 20 * 1024;  // LDS copy of the image descriptors + overlap lists of the walk kernel, when they fit
 constexpr int kStage = FUSION_MEDIAN_STAGE;     // medians: values staged in LDS and ranked by counting; radix select above
 constexpr unsigned long long kCommitted = ~0ull;
-
-struct DevImage {
-  float P[12], inv_P[12], inv_R[9];
-  float sx, sy;          // depth map size / model image size
-  const uint8_t* rgb;    // [bh][bw][3] or nullptr
-  int dw, dh, bw, bh;
-  long long pix_off;     // global offset of the image's first pixel (word / depth / normal arrays)
-  int pos;               // step at which the image is fused; -1: not used
-};
-
-static_assert(sizeof(DevImage) % 8 == 0, "descriptors are copied to LDS word by word and hold 8-byte members");
 
 struct PassCtl {         // device-resident control words of the pass loop (read back once per pass)
   unsigned rstar[2];     // lowest rank that must not commit, slot = pass parity (the other slot is reset by the commit kernel)
@@ -1140,32 +1118,6 @@ struct DevBuf {
   ~DevBuf() { release(); }
 };
 
-// mvs/image.cc:106-135
-void ComposeProjectionMatrix(const float K[9], const float R[9], const float T[3], float P[12]) {
-  float RT[12];
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) RT[4 * r + c] = R[3 * r + c];
-    RT[4 * r + 3] = T[r];
-  }
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 4; ++c) P[4 * r + c] = K[3 * r] * RT[c] + K[3 * r + 1] * RT[4 + c] + K[3 * r + 2] * RT[8 + c];
-}
-
-// top three rows of [P; 0 0 0 1]^-1 = [M^-1 | -M^-1 p], M^-1 by the adjugate
-void ComposeInverseProjectionMatrix(const float P[12], float inv_P[12]) {
-  const float a = P[0], b = P[1], c = P[2], d = P[4], e = P[5], f = P[6], g = P[8], h = P[9], i = P[10];
-  const float A = e * i - f * h, B = -(d * i - f * g), C = d * h - e * g;
-  const float det = a * A + b * B + c * C;
-  const float inv_det = 1.0f / det;
-  const float Mi[9] = {A * inv_det, -(b * i - c * h) * inv_det, (b * f - c * e) * inv_det,
-                       B * inv_det, (a * i - c * g) * inv_det,  -(a * f - c * d) * inv_det,
-                       C * inv_det, -(a * h - b * g) * inv_det, (a * e - b * d) * inv_det};
-  for (int r = 0; r < 3; ++r) {
-    for (int col = 0; col < 3; ++col) inv_P[4 * r + col] = Mi[3 * r + col];
-    inv_P[4 * r + 3] = -(Mi[3 * r] * P[3] + Mi[3 * r + 1] * P[7] + Mi[3 * r + 2] * P[11]);
-  }
-}
-
 struct Stats {
   long long images = 0, seeds = 0, rounds = 0, walks = 0;  // rounds = passes; walks = turns walked (committed or not)
   long long nodes = 0, cuts = 0;                            // pixels recorded by those walks; passes that ended in a cut
@@ -1188,20 +1140,213 @@ int Guard(F&& f) {
   }
 }
 
-}  // namespace
+// Every device buffer of a run, and the Params the kernels read them through. A pointer of Params is bound where its
+// buffer is allocated and nowhere else; the scalars are set by the constructor (the limits of a walk), run_passes (the
+// image's schedule, the pass's window) and resize_spill.
+struct Workspace {
+  Params p;
+  const WalkLimits lim;
+  size_t TT = 0;       // pool threads = waves of the walk kernel
+  unsigned epoch = 1;  // 0 would make the free word look like a mark
+  size_t tmp_bytes = 0, sort_bytes = 0;
+  // resident maps: the bitmaps; all depth maps / normal maps (as xyz triples) / words in one array each, indexed by the
+  // global pixel offset
+  std::vector<DevBuf<uint8_t>> rgb;
+  DevBuf<float> depth, normal, stage;
+  DevBuf<unsigned long long> word;
+  DevBuf<DevImage> img;
+  DevBuf<int> optr, oidx;
+  // per wave
+  DevBuf<unsigned> rec_pix, rec_meta, rec_box, w_tau, w_first, w_count;
+  DevBuf<int> n_walks;
+  DevBuf<float> vals;
+  DevBuf<unsigned long long> spill_goff;
+  DevBuf<uint2> spill_pm;
+  DevBuf<float> spill_d;
+  DevBuf<PassCtl> ctl;
+  // per seed, and the compaction's scratch
+  DevBuf<int> valid, nvis, vis_off, valid_r, nvis_r, scan_valid, scan_vis, pool, out_nvis, out_vis, out_thread;
+  DevBuf<float> pt, out_pt;
+  DevBuf<unsigned char> col, out_col;
+  DevBuf<unsigned char> tmp;
+  DevBuf<unsigned> keys_in, keys_out;
+  DevBuf<int> seeds_in, order;
+  DevBuf<unsigned char> sort_tmp;
 
-struct fusion_result {
-  std::vector<float> xyz_normal;
-  std::vector<uint8_t> rgb;
-  std::vector<int64_t> vis_ptr{0};
-  std::vector<int32_t> vis_idx;
+  explicit Workspace(const WalkLimits& limits) : lim(limits) {
+    std::memset(&p, 0, sizeof(p));
+    p.rec_cap = lim.rec_cap;
+    p.elem_cap = lim.elem_cap;
+    p.max_level = lim.max_level;
+    p.min_num_pixels = lim.min_num_pixels;
+    p.max_depth_error = lim.max_depth_error;
+    p.max_sq_reproj = lim.max_sq_reproj;
+    p.min_cos_normal = lim.min_cos_normal;
+    for (int c = 0; c < 3; ++c) { p.bmin[c] = lim.bmin[c]; p.bmax[c] = lim.bmax[c]; }
+    p.lds_tables = lim.lds_tables;
+    p.wide_group = lim.wide_group;
+    p.wide_bound = lim.wide_bound;
+    p.window_cap = lim.window_max;
+    p.pool_cap = lim.pool_cap;
+  }
+
+  void upload_colours(const RunPlan& plan, const fusion_image* images) {
+    rgb.resize(plan.images.size());
+    for (size_t i = 0; i < rgb.size(); ++i)
+      if (plan.pos[i] >= 0 && images[i].rgb)
+        rgb[i].upload(images[i].rgb, 3 * (size_t)images[i].bitmap_width * images[i].bitmap_height);
+  }
+
+  void alloc_maps(const RunPlan& plan) {
+    depth.alloc((size_t)plan.total_pix); p.depth = depth.p;
+    normal.alloc(3 * (size_t)plan.total_pix); p.normal = normal.p;
+    stage.alloc(3 * (size_t)plan.max_seeds);
+    word.alloc((size_t)plan.total_pix); p.word = word.p;
+    FU_HIP(hipMemset(word.p, 0, sizeof(unsigned long long) * (size_t)plan.total_pix));
+  }
+
+  void upload_maps(const RunPlan& plan, const fusion_image* images) {
+    for (size_t i = 0; i < plan.images.size(); ++i) {
+      if (plan.pos[i] < 0) continue;
+      const size_t npix = (size_t)images[i].depth_width * images[i].depth_height;
+      FU_HIP(hipMemcpy(depth.p + plan.images[i].pix_off, images[i].depth_map, npix * sizeof(float), hipMemcpyHostToDevice));
+      FU_HIP(hipMemcpy(stage.p, images[i].normal_map, 3 * npix * sizeof(float), hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(fusion_normal_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, 0, npix, stage.p,
+                         normal.p + 3 * (size_t)plan.images[i].pix_off);
+      if (images[i].mask) {
+        DevBuf<uint8_t> m;
+        m.upload(images[i].mask, npix);
+        hipLaunchKernelGGL(fusion_premask_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, 0, npix, m.p,
+                           word.p + plan.images[i].pix_off);
+        FU_HIP(hipDeviceSynchronize());
+      }
+      FU_HIP(hipDeviceSynchronize());  // the staging buffer is reused by the next image
+    }
+    stage.release();
+  }
+
+  // image descriptors (with the bitmaps' device pointers) and overlap lists
+  void upload_tables(const RunPlan& plan, const int32_t* h_optr, const int32_t* h_oidx) {
+    const int n = (int)plan.images.size();
+    std::vector<DevImage> h_img = plan.images;
+    for (int i = 0; i < n; ++i) h_img[i].rgb = rgb[i].p;
+    img.upload(h_img.data(), h_img.size()); p.images = img.p;
+    optr.upload(h_optr, (size_t)n + 1); p.optr = optr.p;
+    oidx.upload(h_oidx, (size_t)h_optr[n]); p.oidx = oidx.p;
+    p.n_images = n;
+    p.n_overlap = h_optr[n];
+  }
+
+  void alloc_waves(int max_threads) {
+    TT = (size_t)max_threads;
+    rec_pix.alloc(TT * kRecordBuf); p.rec_pix = rec_pix.p;
+    rec_meta.alloc(TT * kRecordBuf); p.rec_meta = rec_meta.p;
+    rec_box.alloc(TT * kRecordBuf); p.rec_box = rec_box.p;
+    w_tau.alloc(TT * lim.window_max); p.w_tau = w_tau.p;
+    w_first.alloc(TT * lim.window_max); p.w_first = w_first.p;
+    w_count.alloc(TT * lim.window_max); p.w_count = w_count.p;
+    n_walks.alloc(TT); p.n_walks = n_walks.p;
+    vals.alloc(TT * 9 * kRecordBuf); p.vals = vals.p;
+    resize_spill(kStackSpill);
+    ctl.alloc(1); p.ctl = ctl.p;
+  }
+
+  // the stack spill of every wave: at set-up, and again when a walk has overflowed it
+  void resize_spill(int cap) {
+    spill_goff.alloc(TT * cap); p.spill_goff = spill_goff.p;
+    spill_pm.alloc(TT * cap); p.spill_pm = spill_pm.p;
+    spill_d.alloc(TT * cap); p.spill_d = spill_d.p;
+    p.spill_cap = cap;
+  }
+
+  void alloc_outputs(int max_seeds) {
+    const size_t ms = (size_t)max_seeds;
+    valid.alloc(ms); p.valid = valid.p;
+    nvis.alloc(ms); p.nvis = nvis.p;
+    vis_off.alloc(ms); p.vis_off = vis_off.p;
+    valid_r.alloc(ms + 1); nvis_r.alloc(ms + 1);
+    scan_valid.alloc(ms + 1); scan_vis.alloc(ms + 1);
+    pool.alloc((size_t)lim.pool_cap); p.pool = pool.p;
+    out_nvis.alloc(ms); out_vis.alloc((size_t)lim.pool_cap); out_thread.alloc(ms);
+    pt.alloc(6 * ms); p.pt = pt.p;
+    out_pt.alloc(6 * ms);
+    col.alloc(3 * ms); p.col = col.p;
+    out_col.alloc(3 * ms);
+    FU_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, valid_r.p, scan_valid.p, (int)ms + 1));
+    tmp.alloc(tmp_bytes + 16);
+    keys_in.alloc(ms); keys_out.alloc(ms); seeds_in.alloc(ms); order.alloc(ms);
+    FU_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys_in.p, keys_out.p, seeds_in.p, order.p, (int)ms));
+    sort_tmp.alloc(sort_bytes + 16);
+  }
+
+  // all turns of image I, fused at `step`: passes until the window (fusion_plan.h: PassWindow) has reached r_end
+  void run_passes(int step, int I, const Schedule& s) {
+    p.step = step; p.image = I; p.T = s.T; p.W = s.W; p.H = s.H; p.ns = s.ns; p.L = s.L;
+    hipLaunchKernelGGL(fusion_ctl_reset_kernel, dim3(1), dim3(1), 0, 0, ctl.p);
+    FU_HIP(hipMemsetAsync(valid.p, 0, sizeof(int) * (size_t)s.ns_px, 0));
+    PassWindow win(lim.window_first);
+    PassCtl h_ctl;
+    std::memset(&h_ctl, 0, sizeof(h_ctl));
+    for (int pass = 0; win.r_next < s.r_end; ++pass, ++epoch) {
+      FU_CHECK(epoch < 0xFFFFFFFEu, "epoch counter");
+      const Pass ps = win.pass(s);
+      p.epoch = epoch; p.slot = pass & 1;
+      p.tau0 = ps.tau0; p.rmod = ps.rmod; p.tau_end = ps.tau_end; p.limit = ps.limit;
+      hipLaunchKernelGGL(fusion_walk_kernel, dim3(s.T), dim3(kWave), 0, 0, p);
+      hipLaunchKernelGGL(fusion_commit_kernel, dim3(s.T), dim3(kWave * kCommitWaves), 0, 0, p);
+      FU_HIP(hipMemcpy(&h_ctl, ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost));
+      FU_HIP(hipGetLastError());
+      g_stats.rounds += 1;
+      const bool overflowed = (h_ctl.flags & 1u) != 0;
+      if (overflowed) {  // a walk overflowed the stack spill: it cut the pass at its own rank; give it room
+        FU_CHECK((long long)p.spill_cap < lim.spill_bound, "stack overflow beyond its bound");
+        resize_spill((int)std::min<long long>(4ll * p.spill_cap, lim.spill_bound));
+        FU_HIP(hipMemsetAsync(&ctl.p->flags, 0, sizeof(unsigned), 0));
+      }
+      if (win.advance(ps, h_ctl.rstar[pass & 1], overflowed, lim.window_max)) g_stats.cuts += 1;
+    }
+    g_stats.walks += (long long)h_ctl.walks;
+    g_stats.nodes += (long long)h_ctl.nodes;
+    g_stats.redone += (long long)h_ctl.redone;
+    FU_CHECK(h_ctl.cursor <= (unsigned long long)lim.pool_cap, "visibility pool overflow (more than 2^31 - 1 visibility entries for one reference image)");
+  }
+
+  // the image's points in (thread, tick) order, on the device; np / nv: how many, and their visibility entries
+  void compact(const Schedule& s, size_t* np, size_t* nv) {
+    const int ns_px = s.ns_px;
+    hipLaunchKernelGGL(fusion_keys_kernel, dim3((ns_px + 255) / 256), dim3(256), 0, 0, ns_px, s.W, s.T, s.L, s.G, keys_in.p, seeds_in.p);
+    size_t sb = sort_bytes;
+    FU_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp.p, sb, keys_in.p, keys_out.p, seeds_in.p, order.p, ns_px));
+    hipLaunchKernelGGL(fusion_rank_kernel, dim3((ns_px + 256) / 256), dim3(256), 0, 0, ns_px, order.p, valid.p, nvis.p,
+                       valid_r.p, nvis_r.p);
+    size_t tb = tmp_bytes;
+    FU_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, valid_r.p, scan_valid.p, ns_px + 1));
+    tb = tmp_bytes;
+    FU_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, nvis_r.p, scan_vis.p, ns_px + 1));
+    hipLaunchKernelGGL(fusion_compact_kernel, dim3((ns_px + 255) / 256), dim3(256), 0, 0, ns_px, s.W, s.T, order.p, valid_r.p,
+                       scan_valid.p, nvis_r.p, scan_vis.p, vis_off.p, pool.p, pt.p, col.p, out_pt.p, out_col.p,
+                       out_nvis.p, out_vis.p, out_thread.p);
+    int totals[2] = {0, 0};
+    FU_HIP(hipMemcpy(&totals[0], scan_valid.p + ns_px, sizeof(int), hipMemcpyDeviceToHost));
+    FU_HIP(hipMemcpy(&totals[1], scan_vis.p + ns_px, sizeof(int), hipMemcpyDeviceToHost));
+    FU_HIP(hipGetLastError());
+    g_stats.images += 1;
+    g_stats.seeds += ns_px;
+    *np = (size_t)totals[0];
+    *nv = (size_t)totals[1];
+  }
+
+  Chunk read_back(size_t np, size_t nv) {
+    Chunk c;
+    c.pt.resize(6 * np); c.col.resize(3 * np); c.nvis.resize(np); c.vis.resize(nv); c.thread.resize(np);
+    FU_HIP(hipMemcpy(c.pt.data(), out_pt.p, sizeof(float) * 6 * np, hipMemcpyDeviceToHost));
+    FU_HIP(hipMemcpy(c.col.data(), out_col.p, 3 * np, hipMemcpyDeviceToHost));
+    FU_HIP(hipMemcpy(c.nvis.data(), out_nvis.p, sizeof(int) * np, hipMemcpyDeviceToHost));
+    FU_HIP(hipMemcpy(c.thread.data(), out_thread.p, sizeof(int) * np, hipMemcpyDeviceToHost));
+    if (nv) FU_HIP(hipMemcpy(c.vis.data(), out_vis.p, sizeof(int) * nv, hipMemcpyDeviceToHost));
+    return c;
+  }
 };
-
-namespace {
-
-int EnvInt(const char* name, int dflt) {
-  return dev_switch_int(name, dflt);
-}
 
 void Run(const fusion_options& opt, int n, const fusion_image* images, const int32_t* optr, const int32_t* oidx,
          fusion_result* out) {
@@ -1218,305 +1363,40 @@ void Run(const fusion_options& opt, int n, const fusion_image* images, const int
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     throw Fail("no HIP device: the fusion kernels need a GPU (there is no CPU path)");
-  FU_CHECK(n < 65536, "at most 65535 images");
-  FU_CHECK(opt.max_traversal_depth <= 32767, "max_traversal_depth <= 32767");
-  // fusion order (FindNextImage, fusion.cc:51-73): depends on the overlap lists only
-  std::vector<char> used(n, 0), fused(n, 0);
-  for (int i = 0; i < n; ++i) {
-    const fusion_image& im = images[i];
-    if (!im.used) continue;
-    FU_CHECK(im.depth_map && im.normal_map && im.depth_width > 0 && im.depth_height > 0, "depth / normal map");
-    FU_CHECK(im.width > 0 && im.height > 0, "image size");
-    FU_CHECK((int64_t)im.depth_width * im.depth_height < (1ll << 31), "depth map size");
-    used[i] = 1;
-  }
-  std::vector<int> order_of_images, pos(n, -1);
-  if (n > 0) {
-    for (int cur = 0; cur >= 0;) {
-      if (used[cur]) {
-        pos[cur] = (int)order_of_images.size();
-        order_of_images.push_back(cur);
-      }
-      fused[cur] = 1;
-      int nxt = -1;
-      for (int k = optr[cur]; k < optr[cur + 1] && nxt < 0; ++k)
-        if (used[oidx[k]] && !fused[oidx[k]]) nxt = oidx[k];
-      for (int i = 0; i < n && nxt < 0; ++i)
-        if (used[i] && !fused[i]) nxt = i;
-      cur = nxt;
-    }
-  }
-  if (order_of_images.empty()) return;
-  for (int i = 0; i < n; ++i)
-    for (int k = optr[i]; k < optr[i + 1]; ++k) FU_CHECK(oidx[k] >= 0 && oidx[k] < n, "overlap index");
-  int max_overlap = 1;
-  for (int i = 0; i < n; ++i) {
-    FU_CHECK(optr[i + 1] - optr[i] < (1 << 20), "overlap list length");
-    max_overlap = std::max(max_overlap, optr[i + 1] - optr[i]);
-  }
-
-  // resident maps + descriptors
-  std::vector<DevImage> h_img(n);
-  std::vector<DevBuf<uint8_t>> d_rgb(n);
-  long long total_pix = 0;
-  int max_seeds = 0, max_threads = 1, max_height = 1;
-  for (int i = 0; i < n; ++i) {
-    DevImage& d = h_img[i];
-    std::memset(&d, 0, sizeof(d));
-    d.pos = pos[i];
-    if (!used[i]) continue;
-    const fusion_image& im = images[i];
-    const size_t npix = (size_t)im.depth_width * im.depth_height;
-    d.sx = static_cast<float>(im.depth_width) / im.width;
-    d.sy = static_cast<float>(im.depth_height) / im.height;
-    float K[9];
-    std::memcpy(K, im.K, sizeof(K));
-    K[0] *= d.sx; K[2] *= d.sx;
-    K[4] *= d.sy; K[5] *= d.sy;
-    ComposeProjectionMatrix(K, im.R, im.T, d.P);
-    ComposeInverseProjectionMatrix(d.P, d.inv_P);
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) d.inv_R[3 * r + c] = im.R[3 * c + r];
-    if (im.rgb) {
-      FU_CHECK(im.bitmap_width > 0 && im.bitmap_height > 0, "bitmap size");
-      d_rgb[i].upload(im.rgb, 3 * (size_t)im.bitmap_width * im.bitmap_height);
-      d.rgb = d_rgb[i].p;
-    }
-    d.dw = im.depth_width; d.dh = im.depth_height; d.bw = im.bitmap_width; d.bh = im.bitmap_height;
-    d.pix_off = total_pix;
-    total_pix += (long long)npix;
-    max_seeds = std::max(max_seeds, (int)npix);
-    max_height = std::max(max_height, im.depth_height);
-  }
-  // pool threads: one wave each. num_threads <= 0: one thread per stripe (the reference's default pool, all cores, is at
-  // least that large for ordinary images and then behaves the same in step).
-  auto threads_of = [&](int height) {
-    const int ns = (height + kRowStride - 1) / kRowStride;
-    return opt.num_threads <= 0 ? ns : std::min(opt.num_threads, ns);
-  };
-  max_threads = threads_of(max_height);
+  const RunPlan plan = make_plan(opt, n, images, optr, oidx);
+  if (plan.order.empty()) return;
+  Switches sw;
+  sw.lds_tables = dev_switch_int("COLMAP_AMD_FUSION_LDS_TABLES", sw.lds_tables);
+  sw.wide = dev_switch_int("COLMAP_AMD_FUSION_WIDE", sw.wide);  // 0: depth-first walks only; tests compare both
+  sw.window_first = dev_switch_int("COLMAP_AMD_FUSION_WINDOW_FIRST", sw.window_first);
+  sw.window_max = dev_switch_int("COLMAP_AMD_FUSION_WINDOW_MAX", sw.window_max);
+  Workspace ws(make_limits(opt, plan.total_pix, n, optr[n], plan.max_overlap, sw));
+  FU_CHECK(ws.lim.rec_cap <= kRecordBuf, "record buffer of a wave smaller than the record capacity of one walk");
+  ws.upload_colours(plan, images);
   mark("descriptors + colour upload");
-  // all depth maps / normal maps (as xyz triples) / words in one array each, indexed by the global pixel offset
-  DevBuf<float> d_depth, d_normal, d_stage;
-  DevBuf<unsigned long long> d_word;
-  d_depth.alloc((size_t)total_pix);
-  d_normal.alloc(3 * (size_t)total_pix);
-  d_stage.alloc(3 * (size_t)max_seeds);
-  d_word.alloc((size_t)total_pix);
-  FU_HIP(hipMemset(d_word.p, 0, sizeof(unsigned long long) * (size_t)total_pix));
+  ws.alloc_maps(plan);
   mark("map allocations + memset");
-  for (int i = 0; i < n; ++i) {
-    if (!used[i]) continue;
-    const size_t npix = (size_t)images[i].depth_width * images[i].depth_height;
-    FU_HIP(hipMemcpy(d_depth.p + h_img[i].pix_off, images[i].depth_map, npix * sizeof(float), hipMemcpyHostToDevice));
-    FU_HIP(hipMemcpy(d_stage.p, images[i].normal_map, 3 * npix * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(fusion_normal_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, 0, npix, d_stage.p,
-                       d_normal.p + 3 * (size_t)h_img[i].pix_off);
-    if (images[i].mask) {
-      DevBuf<uint8_t> m;
-      m.upload(images[i].mask, npix);
-      hipLaunchKernelGGL(fusion_premask_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, 0, npix, m.p,
-                         d_word.p + h_img[i].pix_off);
-      FU_HIP(hipDeviceSynchronize());
-    }
-    FU_HIP(hipDeviceSynchronize());  // the staging buffer is reused by the next image
-  }
-  d_stage.release();
+  ws.upload_maps(plan, images);
   mark("depth / normal upload");
-  // The visibility pool is refilled per reference image (cursor reset every step) and its int offsets only have to cover
-  // what ONE image's walks absorb: capacity min(total pixels, 2^31 - 1), an overflow fails the run instead of wrapping.
-  const long long pool_cap = std::min<long long>(total_pix, 0x7FFFFFFFll);
-  DevBuf<DevImage> d_img;
-  d_img.upload(h_img.data(), h_img.size());
-  DevBuf<int> d_optr, d_oidx;
-  d_optr.upload(optr, (size_t)n + 1);
-  d_oidx.upload(oidx, (size_t)optr[n]);
-
-  Params p;
-  std::memset(&p, 0, sizeof(p));
-  p.images = d_img.p; p.optr = d_optr.p; p.oidx = d_oidx.p; p.word = d_word.p; p.depth = d_depth.p; p.normal = d_normal.p;
-  p.rec_cap = (int)std::min<long long>(record_capacity(opt.max_num_pixels), std::max<long long>(total_pix, 1));
-  p.elem_cap = std::min(opt.max_num_pixels, p.rec_cap);
-  FU_CHECK(p.rec_cap <= kRecordBuf, "record buffer of a wave smaller than the record capacity of one walk");
-  p.max_level = opt.max_traversal_depth - 1;
-  p.min_num_pixels = opt.min_num_pixels;
-  p.max_depth_error = opt.max_depth_error;
-  p.max_sq_reproj = static_cast<float>(opt.max_reproj_error * opt.max_reproj_error);
-  p.min_cos_normal = static_cast<float>(std::cos(opt.max_normal_error * 0.017453292519943295769));
-  for (int c = 0; c < 3; ++c) { p.bmin[c] = opt.bbox_min[c]; p.bmax[c] = opt.bbox_max[c]; }
-  // per-wave state. Schedule knobs for experiments (the result does not depend on them: bit-exact against the
-  // sequential algorithm for any window): COLMAP_AMD_FUSION_WINDOW_FIRST / _MAX.
-  const int window_first = std::max(1, EnvInt("COLMAP_AMD_FUSION_WINDOW_FIRST", kWindowFirst));
-  const int window_max = std::max(window_first, EnvInt("COLMAP_AMD_FUSION_WINDOW_MAX", kWindowMax));
-  const size_t TT = (size_t)max_threads;
-  DevBuf<unsigned> rec_pix, rec_meta, rec_box, w_tau, w_first, w_count;
-  DevBuf<int> n_walks;
-  DevBuf<float> vals;
-  DevBuf<unsigned long long> spill_goff;
-  DevBuf<uint2> spill_pm;
-  DevBuf<float> spill_d;
-  DevBuf<PassCtl> d_ctl;
-  rec_pix.alloc(TT * kRecordBuf); rec_meta.alloc(TT * kRecordBuf); rec_box.alloc(TT * kRecordBuf);
-  w_tau.alloc(TT * window_max); w_first.alloc(TT * window_max); w_count.alloc(TT * window_max);
-  n_walks.alloc(TT); vals.alloc(TT * 9 * kRecordBuf);
-  int spill_cap = kStackSpill;
-  spill_goff.alloc(TT * spill_cap); spill_pm.alloc(TT * spill_cap); spill_d.alloc(TT * spill_cap);
-  d_ctl.alloc(1);
-  p.rec_pix = rec_pix.p; p.rec_meta = rec_meta.p; p.rec_box = rec_box.p;
-  p.w_tau = w_tau.p; p.w_first = w_first.p; p.w_count = w_count.p; p.n_walks = n_walks.p; p.window_cap = window_max;
-  p.vals = vals.p; p.spill_goff = spill_goff.p; p.spill_pm = spill_pm.p; p.spill_d = spill_d.p; p.spill_cap = spill_cap; p.ctl = d_ctl.p;
-  // LDS copies of the walk kernel: descriptors + overlap offsets, and the overlap lists, when they fit
-  p.n_images = n;
-  p.n_overlap = optr[n];
-  {
-    const size_t desc = (size_t)n * sizeof(DevImage) + ((size_t)n + 1) * sizeof(int);
-    p.lds_tables = desc > (size_t)kTableBytes ? 0 : (desc + (size_t)optr[n] * sizeof(int) > (size_t)kTableBytes ? 1 : 2);
-    p.lds_tables = std::min(p.lds_tables, std::max(0, dev_switch_int("COLMAP_AMD_FUSION_LDS_TABLES", 2)));
-  }
-  // breadth-first walks (walk_turn_wide) where their result provably equals the depth-first one (COLMAP_AMD_FUSION_WIDE=0:
-  // depth-first only; tests compare both)
-  {
-    const int bound = std::min(std::min(p.max_level, p.elem_cap - 1), p.rec_cap);
-    const bool wide = dev_switch_int("COLMAP_AMD_FUSION_WIDE", 1) != 0 && max_overlap <= kWave / 2 && bound >= 16;
-    p.wide_group = wide ? std::max(max_overlap, 1) : 0;
-    p.wide_bound = bound;
-  }
+  ws.upload_tables(plan, optr, oidx);
+  ws.alloc_waves(plan.max_threads);
   mark("per-wave state allocations");
-  // a stack can never hold more than (pixels a walk records) x (longest overlap list) entries
-  const long long spill_bound = (long long)p.rec_cap * max_overlap + kWave;
-
-  DevBuf<int> valid, nvis, vis_off, valid_r, nvis_r, scan_valid, scan_vis, pool, out_nvis, out_vis, out_thread;
-  DevBuf<float> pt, out_pt;
-  DevBuf<unsigned char> col, out_col;
-  const size_t ms = (size_t)max_seeds;
-  valid.alloc(ms); nvis.alloc(ms); vis_off.alloc(ms); valid_r.alloc(ms + 1); nvis_r.alloc(ms + 1);
-  scan_valid.alloc(ms + 1); scan_vis.alloc(ms + 1);
-  pool.alloc((size_t)pool_cap); out_nvis.alloc(ms); out_vis.alloc((size_t)pool_cap); out_thread.alloc(ms);
-  p.pool_cap = pool_cap;
-  pt.alloc(6 * ms); out_pt.alloc(6 * ms); col.alloc(3 * ms); out_col.alloc(3 * ms);
-  p.valid = valid.p; p.nvis = nvis.p; p.vis_off = vis_off.p; p.pt = pt.p; p.col = col.p; p.pool = pool.p;
-  size_t tmp_bytes = 0;
-  FU_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, valid_r.p, scan_valid.p, (int)ms + 1));
-  DevBuf<unsigned char> tmp;
-  tmp.alloc(tmp_bytes + 16);
-  DevBuf<unsigned> keys_in, keys_out;
-  DevBuf<int> seeds_in, order;
-  keys_in.alloc(ms); keys_out.alloc(ms); seeds_in.alloc(ms); order.alloc(ms);
-  size_t sort_bytes = 0;
-  FU_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys_in.p, keys_out.p, seeds_in.p, order.p, (int)ms));
-  DevBuf<unsigned char> sort_tmp;
-  sort_tmp.alloc(sort_bytes + 16);
-
-  // the points of every image, in (thread, tick) order, with their thread; concatenated per thread at the end
-  struct Chunk {
-    std::vector<float> pt;
-    std::vector<unsigned char> col;
-    std::vector<int> nvis, vis, thread;
-  };
-  std::vector<Chunk> chunks;
-  unsigned epoch = 1;  // 0 would make the free word look like a mark
+  ws.alloc_outputs(plan.max_seeds);
   mark("scratch allocations");
   g_stats = Stats();
   FU_HIP(hipDeviceSynchronize());
   const auto t_setup = std::chrono::steady_clock::now();
   g_stats.upload_seconds = std::chrono::duration<double>(t_setup - t_begin).count();
-  for (int step = 0; step < (int)order_of_images.size(); ++step) {
-    const int I = order_of_images[step];
-    const int W = h_img[I].dw, H = h_img[I].dh, ns_px = W * H;
-    const int ns = (H + kRowStride - 1) / kRowStride, T = threads_of(H), G = (ns + T - 1) / T;
-    const unsigned long long L = (unsigned long long)kRowStride * W, ticks = (unsigned long long)G * L;
-    const unsigned long long r_end = ticks * (unsigned long long)T;
-    FU_CHECK(r_end < 0xFFFFFFF0ull, "turns of one image < 2^32");
-    p.step = step; p.image = I; p.T = T; p.W = W; p.H = H; p.ns = ns; p.L = (unsigned)L;
-    hipLaunchKernelGGL(fusion_ctl_reset_kernel, dim3(1), dim3(1), 0, 0, d_ctl.p);
-    FU_HIP(hipMemsetAsync(valid.p, 0, sizeof(int) * (size_t)ns_px, 0));
-    // passes: ranks [r_next, limit) are walked speculatively, [r_next, rstar) commit
-    unsigned long long r_next = 0;
-    long long window = window_first;
-    PassCtl h_ctl;
-    std::memset(&h_ctl, 0, sizeof(h_ctl));
-    for (int pass = 0; r_next < r_end; ++pass, ++epoch) {
-      FU_CHECK(epoch < 0xFFFFFFFEu, "epoch counter");
-      const unsigned long long tau0 = r_next / (unsigned long long)T;
-      const unsigned long long tau_end = std::min<unsigned long long>(tau0 + (unsigned long long)window, ticks);
-      p.epoch = epoch; p.slot = pass & 1;
-      p.tau0 = (unsigned)tau0; p.rmod = (unsigned)(r_next % (unsigned long long)T);
-      p.tau_end = (unsigned)tau_end; p.limit = (unsigned)(tau_end * (unsigned long long)T);
-      hipLaunchKernelGGL(fusion_walk_kernel, dim3(T), dim3(kWave), 0, 0, p);
-      hipLaunchKernelGGL(fusion_commit_kernel, dim3(T), dim3(kWave * kCommitWaves), 0, 0, p);
-      FU_HIP(hipMemcpy(&h_ctl, d_ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost));
-      FU_HIP(hipGetLastError());
-      const unsigned long long rstar = std::min<unsigned long long>(h_ctl.rstar[pass & 1], p.limit);
-      g_stats.rounds += 1;
-      if (h_ctl.flags & 1u) {  // a walk overflowed the stack spill: it cut the pass at its own rank; give it room
-        FU_CHECK((long long)spill_cap < spill_bound, "stack overflow beyond its bound");
-        spill_cap = (int)std::min<long long>(4ll * spill_cap, spill_bound);
-        spill_goff.alloc(TT * spill_cap); spill_pm.alloc(TT * spill_cap); spill_d.alloc(TT * spill_cap);
-        p.spill_goff = spill_goff.p; p.spill_pm = spill_pm.p; p.spill_d = spill_d.p; p.spill_cap = spill_cap;
-        FU_HIP(hipMemsetAsync(&d_ctl.p->flags, 0, sizeof(unsigned), 0));
-      } else {
-        FU_CHECK(rstar > r_next, "pass made no progress");
-      }
-      const bool cut = rstar < (unsigned long long)p.limit;
-      if (cut) g_stats.cuts += 1;
-      window = cut ? std::max<long long>(kWindowMin, window / 2) : std::min<long long>(window_max, 2 * window);
-      r_next = rstar;
-    }
-    g_stats.walks += (long long)h_ctl.walks;
-    g_stats.nodes += (long long)h_ctl.nodes;
-    g_stats.redone += (long long)h_ctl.redone;
-    FU_CHECK(h_ctl.cursor <= (unsigned long long)pool_cap, "visibility pool overflow (more than 2^31 - 1 visibility entries for one reference image)");
-    // output order of this image: (thread, tick)
-    hipLaunchKernelGGL(fusion_keys_kernel, dim3((ns_px + 255) / 256), dim3(256), 0, 0, ns_px, W, T, (unsigned)L, G, keys_in.p, seeds_in.p);
-    size_t sb = sort_bytes;
-    FU_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp.p, sb, keys_in.p, keys_out.p, seeds_in.p, order.p, ns_px));
-    hipLaunchKernelGGL(fusion_rank_kernel, dim3((ns_px + 256) / 256), dim3(256), 0, 0, ns_px, order.p, valid.p, nvis.p,
-                       valid_r.p, nvis_r.p);
-    size_t tb = tmp_bytes;
-    FU_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, valid_r.p, scan_valid.p, ns_px + 1));
-    tb = tmp_bytes;
-    FU_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, nvis_r.p, scan_vis.p, ns_px + 1));
-    hipLaunchKernelGGL(fusion_compact_kernel, dim3((ns_px + 255) / 256), dim3(256), 0, 0, ns_px, W, T, order.p, valid_r.p,
-                       scan_valid.p, nvis_r.p, scan_vis.p, vis_off.p, pool.p, pt.p, col.p, out_pt.p, out_col.p,
-                       out_nvis.p, out_vis.p, out_thread.p);
-    int totals[2] = {0, 0};
-    FU_HIP(hipMemcpy(&totals[0], scan_valid.p + ns_px, sizeof(int), hipMemcpyDeviceToHost));
-    FU_HIP(hipMemcpy(&totals[1], scan_vis.p + ns_px, sizeof(int), hipMemcpyDeviceToHost));
-    FU_HIP(hipGetLastError());
-    g_stats.images += 1;
-    g_stats.seeds += ns_px;
-    const size_t np = (size_t)totals[0], nv = (size_t)totals[1];
-    if (np == 0) continue;
-    chunks.emplace_back();
-    Chunk& c = chunks.back();
-    c.pt.resize(6 * np); c.col.resize(3 * np); c.nvis.resize(np); c.vis.resize(nv); c.thread.resize(np);
-    FU_HIP(hipMemcpy(c.pt.data(), out_pt.p, sizeof(float) * 6 * np, hipMemcpyDeviceToHost));
-    FU_HIP(hipMemcpy(c.col.data(), out_col.p, 3 * np, hipMemcpyDeviceToHost));
-    FU_HIP(hipMemcpy(c.nvis.data(), out_nvis.p, sizeof(int) * np, hipMemcpyDeviceToHost));
-    FU_HIP(hipMemcpy(c.thread.data(), out_thread.p, sizeof(int) * np, hipMemcpyDeviceToHost));
-    if (nv) FU_HIP(hipMemcpy(c.vis.data(), out_vis.p, sizeof(int) * nv, hipMemcpyDeviceToHost));
+  std::vector<Chunk> chunks;
+  for (int step = 0; step < (int)plan.order.size(); ++step) {
+    const int I = plan.order[step];
+    const Schedule s = make_schedule(plan.images[I].dw, plan.images[I].dh, opt.num_threads);
+    ws.run_passes(step, I, s);
+    size_t np = 0, nv = 0;
+    ws.compact(s, &np, &nv);
+    if (np) chunks.push_back(ws.read_back(np, nv));
   }
-  // task_fused_points_[thread] concatenated over the threads (fusion.cc:322-337): every chunk is sorted by thread
-  std::vector<size_t> at(chunks.size(), 0), vat(chunks.size(), 0);
-  for (int t = 0; t < max_threads; ++t) {
-    for (size_t ci = 0; ci < chunks.size(); ++ci) {
-      const Chunk& c = chunks[ci];
-      const size_t b = at[ci];
-      size_t e = b, nv = 0;
-      while (e < c.thread.size() && c.thread[e] == t) nv += (size_t)c.nvis[e++];
-      if (e == b) continue;
-      out->xyz_normal.insert(out->xyz_normal.end(), c.pt.begin() + 6 * b, c.pt.begin() + 6 * e);
-      out->rgb.insert(out->rgb.end(), c.col.begin() + 3 * b, c.col.begin() + 3 * e);
-      out->vis_idx.insert(out->vis_idx.end(), c.vis.begin() + vat[ci], c.vis.begin() + vat[ci] + nv);
-      int64_t base = out->vis_ptr.back();
-      for (size_t k = b; k < e; ++k) {
-        base += c.nvis[k];
-        out->vis_ptr.push_back(base);
-      }
-      at[ci] = e;
-      vat[ci] += nv;
-    }
-  }
+  concatenate(chunks, plan.max_threads, out);
   g_stats.device_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup).count();
 }
 

@@ -30,8 +30,8 @@ class _EmulEntryPoints:
 
     def __init__(self, name):
         path = os.path.join(_HERE, name)
-        deps = [_SRC, os.path.join(_HERE, "hip", "hip_runtime.h"), os.path.join(_HERE, "hipcub", "hipcub.hpp"),
-                os.path.join(_HERE, "build.sh")]
+        deps = [_SRC, os.path.join(os.path.dirname(_SRC), "fusion_plan.h"), os.path.join(_HERE, "hip", "hip_runtime.h"),
+                os.path.join(_HERE, "hipcub", "hipcub.hpp"), os.path.join(_HERE, "build.sh")]
         if not _EmulEntryPoints._built and (not os.path.exists(path) or
                                             any(os.path.getmtime(d) > os.path.getmtime(path) for d in deps)):
             subprocess.check_call(["sh", os.path.join(_HERE, "build.sh")])
