@@ -6,6 +6,7 @@ COMMANDS = {
     "patch_match_stereo": ("colmap_amd.patch_match_stereo", "dense stereo on an undistorted workspace (exe/mvs.cc:228-279)"),
     "stereo_fusion": ("colmap_amd.fusion", "fuse depth / normal maps into a point cloud (exe/mvs.cc:299-386)"),
     "bundle_adjuster": ("colmap_amd.bundle_adjuster", "global bundle adjustment of a sparse model (exe/sfm.cc:175-206)"),
+    "point_filtering": ("colmap_amd.point_filtering", "filter outlier observations and points of a sparse model (exe/sfm.cc:556-587)"),
     "image_undistorter": ("colmap_amd.image_undistorter", "undistort images into a dense workspace (exe/image.cc:325-430)"),
 }
 

@@ -160,9 +160,15 @@ def point3D_errors(rec: scene.Reconstruction) -> dict:
     return out
 
 
-def update_sparse_model(sm: W.SparseModel, rec: scene.Reconstruction):
+def _device_index(gpu_index) -> int:
+    """The first device of a `gpu_index` option ("-1" = default device 0)."""
+    first = int(str(gpu_index).split(",")[0])
+    return 0 if first < 0 else first
+
+
+def update_sparse_model(sm: W.SparseModel, rec: scene.Reconstruction, errors: Optional[dict] = None):
     """Reconstruction -> files: poses, intrinsics, points, tracks (observations may have been
-    deleted), point errors."""
+    deleted), point errors (`errors` when the caller has computed them, point3D_errors otherwise)."""
     for cid, c in rec.cameras.items():
         sm.cameras[cid].params = np.array(c.params, np.float64)
     for iid, img in rec.images.items():
@@ -185,7 +191,7 @@ def update_sparse_model(sm: W.SparseModel, rec: scene.Reconstruction):
                 rfw = cfw if sfr is None else scene.rigid_compose(_rigid_inverse(sfr), cfw)
                 fr.rig_from_world = _wxyz_t(rfw)
                 break
-    errs = point3D_errors(rec)
+    errs = point3D_errors(rec) if errors is None else errors
     for pid in list(sm.points3D):
         if pid not in rec.points3D:
             del sm.points3D[pid]
@@ -210,7 +216,12 @@ class BundleAdjustmentController:
         if len(rec.images) == 0:
             print("E Need at least one registered frame.", file=sys.stderr)
             return
-        self.num_filtered_observations = filter_observations_with_negative_depth(rec)
+        if self._solve_fn is None:  # the product path: the filter runs on the device (include/colmap_amd_obs.h)
+            from . import observation_manager as OM
+            self.num_filtered_observations = OM.ObservationManager(
+                rec, gpu_index=_device_index(self.options_.gpu_index)).FilterObservationsWithNegativeDepth()
+        else:
+            self.num_filtered_observations = filter_observations_with_negative_depth(rec)
         config = est.BundleAdjustmentConfig()
         for image_id in rec.RegImageIds():
             config.AddImage(image_id)
@@ -279,7 +290,11 @@ def main(argv=None, solve_fn=None) -> int:
     ctl.Run()
     if ctl.summary is not None:
         print(ctl.summary.BriefReport())
-    update_sparse_model(sm, rec)
+    errors = None
+    if solve_fn is None and ctl.summary is not None:  # UpdatePoint3DErrors on the device, like the solve
+        from . import observation_manager as OM
+        errors = OM.point3D_errors(rec, gpu_index=_device_index(a.gpu_index))
+    update_sparse_model(sm, rec, errors)
     W.write_model_binary(sm, a.output_path)
     return 0
 

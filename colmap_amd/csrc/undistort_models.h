@@ -5,6 +5,9 @@
 //                                             operations, together with its ANALYTIC Jacobian d(du, dv) / d(u, v)
 //                                             (the reference differentiates with ceres::Jet, models.h:1157-1174)
 //   img_from_normalized()                     ImgFromCam(u, v, w = 1) with the validity rules of each model
+//   img_from_cam()                            ImgFromCam(u, v, w) with each model's own validity / cheirality rule
+//   cam_ray_from_img()                        CamRayFromImg: the unit bearing of a pixel (the whole sphere for
+//                                             EQUIRECTANGULAR)
 //   cam_from_img()                            CamFromImg: closed forms where the reference has them (pinholes, FOV,
 //                                             division models, SIMPLE_FISHEYE / FISHEYE, EUCM), IterativeUndistortion
 //                                             (models.h:1141-1197) for the rest
@@ -385,6 +388,65 @@ UD_HD bool cam_from_img(int m, const double* p, double x, double y, double* u, d
       return true;
     }
   }
+}
+
+// CameraModel::ImgFromCam(u, v, w, check_cheirality = true) with each model's own validity rule:
+//   the division models take any depth (models.h:2405-2436, 2494-2526: the quadratic is solved with w itself),
+//   EUCM wants w >= epsilon AND its denominator >= epsilon (:2757-2794),
+//   EQUIRECTANGULAR takes every direction but the zero vector (:2852-2877),
+//   every other model wants HasProjectableDepth(w) = w >= epsilon (:281-285) and then projects (u / w, v / w).
+UD_HD bool img_from_cam(int m, const double* p, double u, double v, double w, double* x, double* y) {
+  if (m == EQUIRECTANGULAR) {
+    const double horizontal = sqrt(u * u + w * w);
+    if (horizontal + fabs(v) < kEps) return false;
+    *x = (atan2(u, w) / (2.0 * kPi) + 0.5) * p[0];
+    *y = (0.5 - atan2(-v, horizontal) / kPi) * p[1];
+    return true;
+  }
+  if (m == SIMPLE_DIVISION || m == DIVISION) {
+    const Intrinsics k = intrinsics(m, p);
+    const double rho = sqrt(u * u + v * v);
+    const double disc_sq = w * w - 4.0 * rho * rho * k.extra[0];
+    if (disc_sq < 0.0) return false;
+    const double r = 2.0 / (w + sqrt(disc_sq));
+    *x = k.f1 * r * u + k.c1;
+    *y = k.f2 * r * v + k.c2;
+    return true;
+  }
+  if (!(w >= kEps)) return false;
+  if (m == EUCM) {
+    const Intrinsics k = intrinsics(m, p);
+    const double alpha = k.extra[0], beta = k.extra[1];
+    const double rho2 = beta * (u * u + v * v) + w * w;
+    if (rho2 < 0.0) return false;
+    const double den = alpha * sqrt(rho2) + (1.0 - alpha) * w;
+    if (!(den >= kEps)) return false;
+    *x = k.f1 * (u / den) + k.c1;
+    *y = k.f2 * (v / den) + k.c2;
+    return true;
+  }
+  return img_from_normalized(m, p, u / w, v / w, x, y);
+}
+
+// CameraModel::CamRayFromImg: the unit bearing of a pixel. EQUIRECTANGULAR covers the whole sphere and always has a
+// value (models.h:813-828); every other model normalises (CamFromImg, 1) (:353-369).
+UD_HD bool cam_ray_from_img(int m, const double* p, double x, double y, double* rx, double* ry, double* rz) {
+  if (m == EQUIRECTANGULAR) {
+    const double theta = 2.0 * kPi * (x / p[0] - 0.5);
+    const double phi = kPi * (0.5 - y / p[1]);
+    const double cos_phi = cos(phi);
+    *rx = cos_phi * sin(theta);
+    *ry = -sin(phi);
+    *rz = cos_phi * cos(theta);
+    return true;
+  }
+  double u, v;
+  if (!cam_from_img(m, p, x, y, &u, &v)) return false;
+  const double norm = sqrt(u * u + v * v + 1.0);
+  *rx = u / norm;
+  *ry = v / norm;
+  *rz = 1.0 / norm;
+  return true;
 }
 
 }  // namespace undistort

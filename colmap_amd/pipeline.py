@@ -1,5 +1,5 @@
 """pycolmap-style pipeline functions on the MI355X paths: `from colmap_amd.pipeline import
-patch_match_stereo, stereo_fusion, bundle_adjustment, undistort_images`."""
+patch_match_stereo, stereo_fusion, bundle_adjustment, filter_points, undistort_images`."""
 # ---------------------------------------------------------------------------------------------
 # pycolmap-style pipeline functions (reference pycolmap/pipeline/mvs.cc:119-127,182-193,
 # pycolmap/pipeline/sfm.cc:153-161,258-263): same names, argument order and defaults. Imports are
@@ -44,6 +44,14 @@ def bundle_adjustment(reconstruction, options=None):
     ctl = bundle_adjuster.BundleAdjustmentController(options or estimators.BundleAdjustmentOptions(), reconstruction)
     ctl.Run()
     return ctl.summary
+
+
+def filter_points(reconstruction, max_reproj_error=4.0, min_tri_angle=1.5, min_track_len=2, gpu_index=0):
+    """`colmap point_filtering` on a colmap_amd.scene.Reconstruction, in place (needs an MI355X):
+    ObservationManager.FilterAllPoints3D, then FilterPoints3DWithShortTracks; returns the filtered-observation count."""
+    from . import observation_manager
+    om = observation_manager.ObservationManager(reconstruction, gpu_index=gpu_index)
+    return om.FilterAllPoints3D(max_reproj_error, min_tri_angle) + om.FilterPoints3DWithShortTracks(min_track_len)
 
 
 def estimate_ba_covariance(options, reconstruction, bundle_adjuster):

@@ -111,6 +111,10 @@ def rigid_compose(a: np.ndarray, b: np.ndarray) -> np.ndarray:
 class Point3D:
     xyz: np.ndarray
     track: List[Tuple[int, int]] = field(default_factory=list)  # (image_id, point2D_idx)
+    error: float = -1.0  # mean reprojection error in pixels; -1 = none yet (Point3D::HasError, scene/point3d.h)
+
+    def HasError(self) -> bool:
+        return self.error != -1.0
 
 
 class Reconstruction:
@@ -211,6 +215,32 @@ class Reconstruction:
             return
         pt.track.remove((image_id, point2D_idx))
         p2.point3D_id = -1
+
+    def DeletePoint3D(self, point3D_id: int):
+        """Reconstruction::DeletePoint3D: the observations of the track lose their point, the point goes."""
+        for (im, idx) in self.points3D[point3D_id].track:
+            self.images[im].points2D[idx].point3D_id = -1
+        del self.points3D[point3D_id]
+
+    def UpdatePoint3DErrors(self, gpu_index: int = 0):
+        """Reconstruction::UpdatePoint3DErrors (scene/reconstruction.cc:959-975) on the device (obs_point_errors,
+        include/colmap_amd_obs.h): Point3D.error = mean reprojection error over the track, 0 for an empty track."""
+        from . import observation_manager
+        for pid, e in observation_manager.point3D_errors(self, gpu_index=gpu_index).items():
+            self.points3D[pid].error = e
+
+    def ComputeNumObservations(self) -> int:
+        """Reconstruction::ComputeNumObservations (:918-924): observations with a 3-D point over the registered images."""
+        return sum(1 for img in self.images.values() for p in img.points2D if p.HasPoint3D())
+
+    def ComputeMeanTrackLength(self) -> float:
+        """Reconstruction::ComputeMeanTrackLength (:926-932)."""
+        return self.ComputeNumObservations() / len(self.points3D) if self.points3D else 0.0
+
+    def ComputeMeanReprojectionError(self) -> float:
+        """Reconstruction::ComputeMeanReprojectionError (:942-957): mean over the points that have an error."""
+        errs = [p.error for p in self.points3D.values() if p.HasError()]
+        return sum(errs) / len(errs) if errs else 0.0
 
     def copy(self) -> "Reconstruction":
         return copy.deepcopy(self)
