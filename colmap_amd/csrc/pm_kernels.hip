@@ -168,6 +168,14 @@ __device__ __forceinline__ void normal_from_sweep(int rot, float sx, float sy, f
   }
 }
 
+// Depth and normal of a pixel the filter rejects (:1267-1275): zeros, the normal written in the sweep frame like any other
+// -- the reference rotates the zeroed map back, so a component the signed swap negates reads -0.0f.
+__device__ __forceinline__ void store_filtered_zero(const PmParams& p, float* rec) {
+  float nx, ny;
+  normal_from_sweep(p.rot, 0.0f, 0.0f, nx, ny);
+  rec[0] = 0.0f; rec[1] = nx; rec[2] = ny; rec[3] = 0.0f;
+}
+
 // reference-image texel in the sweep frame: point fetch, border 0, /255
 __device__ __forceinline__ float ref_texel(const PmParams& p, int row, int col) {
   if (row < 0 || col < 0 || row >= rot_height(p) || col >= rot_width(p)) return 0.0f;
@@ -1481,8 +1489,7 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
         for (int s = 0; s < S; ++s) num += L.flags[c * S + s];
         const int pix = pix_index(p, row, col0 + c);
         if (num < p.filter_min_num_consistent) {
-          float* rec = p.rec + (size_t)pix * p.rec_stride;
-          rec[0] = 0.0f; rec[1] = 0.0f; rec[2] = 0.0f; rec[3] = 0.0f;
+          store_filtered_zero(p, p.rec + (size_t)pix * p.rec_stride);
         } else {
           for (int s = 0; s < S; ++s)
             if (L.flags[c * S + s]) p.mask[(size_t)s * p.W * p.H + pix] = 1;
@@ -2244,8 +2251,7 @@ __device__ __forceinline__ void sweep_wave_body(const PmParams* __restrict__ pp)
         for (int s = 0; s < S; ++s) num += L.flags[c * S + s];
         const int pix = pix_index(p, row, col0 + c);
         if (num < p.filter_min_num_consistent) {
-          float* rec = p.rec + (size_t)pix * p.rec_stride;
-          rec[0] = 0.0f; rec[1] = 0.0f; rec[2] = 0.0f; rec[3] = 0.0f;
+          store_filtered_zero(p, p.rec + (size_t)pix * p.rec_stride);
         } else {
           for (int s = 0; s < S; ++s)
             if (L.flags[c * S + s]) p.mask[(size_t)s * p.W * p.H + pix] = 1;

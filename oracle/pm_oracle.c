@@ -55,6 +55,54 @@
 #define PMO_API __attribute__((visibility("default")))
 
 /* ------------------------------------------------------------------------- */
+/* Census (optional): which of the rarely taken paths did a run take?        */
+/* ------------------------------------------------------------------------- */
+/* Compiled only with -DPMO_CENSUS, into a SECOND library (oracle/Makefile: libpm_oracle_census.so); in the plain build
+ * both macros expand to nothing and the object code is the one it was. The counters only observe -- the census build
+ * returns the bits of the plain build (tests/test_pm_oracle.py asserts it) -- and are process-wide sums over every
+ * evaluation the oracle performs (memoised values are counted once, when they are computed). Order of the names =
+ * CENSUS_FIELDS in oracle/pm_oracle.py. */
+enum {
+  PMC_TAPS,                /* bilinear source samples taken by the NCC */
+  PMC_TAP_BORDER,          /* ... of which at least one of the four texels is the zero border */
+  PMC_TAP_OUTSIDE,         /* ... of which all four are */
+  PMC_COORD_SATURATED,     /* tap coordinates at or beyond +-2^31 (the float -> int conversion saturates) */
+  PMC_COORD_NONFINITE,     /* tap coordinates that are NaN or +-inf */
+  PMC_NCC_EVALS,           /* NCC evaluations */
+  PMC_NCC_CUT_REF_VAR,     /* ... returned 2.0 because the reference patch variance is below 1e-5 */
+  PMC_NCC_CUT_SRC_VAR,     /* ... returned 2.0 because (only) the source patch variance is below 1e-5 */
+  PMC_NCC_SRC_VAR_NAN,     /* ... whose source variance is a NaN (compares false: not cut) */
+  PMC_NCC_REF_VAR_AT_CUT,  /* ... whose reference variance EQUALS 1e-5f: not cut, what tells `<` from `<=` */
+  PMC_CORNER_DIV_NONPOS,   /* window corners whose projective divisor is not > 0 (<= 0 or NaN) */
+  PMC_PROB_SUM_ZERO,       /* view-selection steps whose prob_sum is 0 */
+  PMC_CDF_NAN,             /* view-selection steps whose CDF holds a NaN */
+  PMC_CDF_NAN_AFTER_VALUE, /* ... whose CDF holds a non-NaN entry in front of its first NaN */
+  PMC_SRC_DEPTH_ZERO,      /* source-depth fetches that return 0 (holes and the border) */
+  PMC_SRC_DEPTH_NEGATIVE,  /* ... a negative value */
+  PMC_SRC_DEPTH_NONFINITE, /* ... NaN or +-inf */
+  PMC_PROPAGATE_NONPOS,    /* PropagateDepth results <= 0 */
+  PMC_PROPAGATE_NONFINITE, /* PropagateDepth results NaN or +-inf */
+  PMC_PERTURB_EXHAUSTED,   /* PerturbNormal gave up after its retries and kept the input normal */
+  PMC_COUNT
+};
+#ifdef PMO_CENSUS
+static uint64_t g_census[PMC_COUNT];
+#define CENSUS(i) ((void)__atomic_fetch_add(&g_census[i], (uint64_t)1, __ATOMIC_RELAXED))
+#define CENSUS_IF(cond, i) do { if (cond) CENSUS(i); } while (0)
+/* copies min(n, PMC_COUNT) counters to out (NULL: none), clears all of them if `reset`; returns PMC_COUNT */
+PMO_API int pmo_census(uint64_t* out, int n, int reset) {
+  for (int i = 0; i < PMC_COUNT; ++i) {
+    if (out && i < n) out[i] = __atomic_load_n(&g_census[i], __ATOMIC_RELAXED);
+    if (reset) __atomic_store_n(&g_census[i], (uint64_t)0, __ATOMIC_RELAXED);
+  }
+  return PMC_COUNT;
+}
+#else
+#define CENSUS(i) ((void)0)
+#define CENSUS_IF(cond, i) ((void)0)
+#endif
+
+/* ------------------------------------------------------------------------- */
 /* Public structs (flat, ctypes-friendly)                                    */
 /* ------------------------------------------------------------------------- */
 
@@ -316,6 +364,21 @@ static inline float tex_src_point(const pmo_state* st, int s, int ix, int iy) {
   return st->lut[st->src_images[((size_t)s * st->src_h + iy) * st->src_w + ix]];
 }
 
+/* census of one bilinear sample: coordinates as given, (ix, iy) the converted floor */
+#ifdef PMO_CENSUS
+static inline void census_tap(const pmo_state* st, float x, float y, float fx, float fy, int ix, int iy) {
+  CENSUS(PMC_TAPS);
+  CENSUS_IF(!(fabsf(x) <= FLT_MAX) || !(fabsf(y) <= FLT_MAX), PMC_COORD_NONFINITE);
+  CENSUS_IF(fabsf(fx) >= 2147483648.0f || fabsf(fy) >= 2147483648.0f, PMC_COORD_SATURATED);
+  const int x_in0 = ix >= 0 && ix < st->src_w, x_in1 = ix != INT32_MAX && ix + 1 >= 0 && ix + 1 < st->src_w;
+  const int y_in0 = iy >= 0 && iy < st->src_h, y_in1 = iy != INT32_MAX && iy + 1 >= 0 && iy + 1 < st->src_h;
+  CENSUS_IF(!(x_in0 && x_in1 && y_in0 && y_in1), PMC_TAP_BORDER);
+  CENSUS_IF(!((x_in0 || x_in1) && (y_in0 || y_in1)), PMC_TAP_OUTSIDE);
+}
+#else
+#define census_tap(st, x, y, fx, fy, ix, iy) ((void)0)
+#endif
+
 /* SampleLayeredBilinear, patch_match_cuda.cu:426-442 */
 static inline float tex_src_bilinear(const pmo_state* st, int s, float x, float y) {
   const float px = x - 0.5f;
@@ -329,6 +392,7 @@ static inline float tex_src_bilinear(const pmo_state* st, int s, float x, float 
   /* guard +1 overflow at INT32_MAX */
   const int ix1 = ix == INT32_MAX ? ix : ix + 1;
   const int iy1 = iy == INT32_MAX ? iy : iy + 1;
+  census_tap(st, px, py, fx, fy, ix, iy);
   const float c00 = tex_src_point(st, s, ix, iy);
   const float c10 = tex_src_point(st, s, ix1, iy);
   const float c01 = tex_src_point(st, s, ix, iy1);
@@ -357,6 +421,7 @@ static inline float tex_src_bilinear_raw(const pmo_state* st, int s, float px, f
   const int iy = sat_f2i(fy);
   const int ix1 = ix == INT32_MAX ? ix : ix + 1;
   const int iy1 = iy == INT32_MAX ? iy : iy + 1;
+  census_tap(st, px, py, fx, fy, ix, iy);
   const float c00 = tex_src_raw(st, s, ix, iy);
   const float c10 = tex_src_raw(st, s, ix1, iy);
   const float c01 = tex_src_raw(st, s, ix, iy1);
@@ -440,6 +505,7 @@ static void perturb_normal(const float inv_K[4], int row, int col, float perturb
         perturbation = 0.5f * perturbation;
         continue;
       }
+      CENSUS(PMC_PERTURB_EXHAUSTED);
       out[0] = normal[0]; out[1] = normal[1]; out[2] = normal[2];
       return;
     }
@@ -524,6 +590,33 @@ typedef struct {
   int radius, step;
 } ncc_params;
 
+/* census of one NCC evaluation: which side of the variance cut-off it falls on */
+#ifdef PMO_CENSUS
+static inline void census_ncc(float ref_color_var, float src_color_var) {
+  CENSUS(PMC_NCC_EVALS);
+  CENSUS_IF(ref_color_var < 1e-5f, PMC_NCC_CUT_REF_VAR);
+  CENSUS_IF(!(ref_color_var < 1e-5f) && src_color_var < 1e-5f, PMC_NCC_CUT_SRC_VAR);
+  CENSUS_IF(src_color_var != src_color_var, PMC_NCC_SRC_VAR_NAN);
+  CENSUS_IF(ref_color_var == 1e-5f, PMC_NCC_REF_VAR_AT_CUT);
+}
+#else
+#define census_ncc(ref_color_var, src_color_var) ((void)0)
+#endif
+
+/* census of the projective divisor at the four corners of the window (what decides between the device's unclamped and
+ * clamped gathers, pm_kernels.hip: patch_inside) */
+#ifdef PMO_CENSUS
+static inline void census_corners(const float tf[9], int radius, int row, int col) {
+  for (int k = 0; k < 4; ++k) {
+    const float x = (float)(col + ((k & 1) ? radius : -radius)), y = (float)(row + ((k & 2) ? radius : -radius));
+    const float z = fmaf(tf[6], x, fmaf(tf[7], y, tf[8]));
+    CENSUS_IF(!(z > 0.0f), PMC_CORNER_DIV_NONPOS);
+  }
+}
+#else
+#define census_corners(tf, radius, row, col) ((void)0)
+#endif
+
 /* PhotoConsistencyCostComputer::Compute, patch_match_cuda.cu:489-593.
  * `weights`/`refc` (optional, both or neither): the (2r/step+1)^2 bilateral
  * weights and reference colours of the patch centred at (row, col), precomputed
@@ -535,6 +628,7 @@ static float ncc_cost(const pmo_state* st, const ncc_params* np, const float inv
                       const float* weights, const float* refc) {
   float tform[9];
   compose_homography(inv_K, pose, row, col, depth, normal, tform);
+  census_corners(tform, np->radius, row, col);
   const int kWindowStep = np->step;
   const int kWindowRadius = np->radius;
   float tform_step[8];
@@ -590,6 +684,7 @@ static float ncc_cost(const pmo_state* st, const ncc_params* np, const float inv
   const float src_color_var = src_color_squared_sum - src_color_sum * src_color_sum;
   const float kMinVar = 1e-5f;
   const float kMaxCost = 2.0f;
+  census_ncc(ref_color_var, src_color_var);
   if (ref_color_var < kMinVar || src_color_var < kMinVar) return kMaxCost;
   const float covar = src_ref_color_sum - ref_sum * src_color_sum;
   const float var = sqrtf(ref_color_var * src_color_var);
@@ -773,6 +868,7 @@ static float ncc_cost_device_mixed(const pmo_state* st, const ncc_params* np, co
   src_ref_color_sum *= inv_bws;
   const float ref_color_var = ref_sqsum - ref_sum * ref_sum;
   const float src_color_var = src_color_squared_sum - src_color_sum * src_color_sum;
+  census_ncc(ref_color_var, src_color_var);
   if (ref_color_var < 1e-5f || src_color_var < 1e-5f) return 2.0f;
   const float covar = src_ref_color_sum - ref_sum * src_color_sum;
   const float var = sqrtf(ref_color_var * src_color_var);
@@ -785,6 +881,7 @@ static float ncc_cost_device(const pmo_state* st, const ncc_params* np, const fl
                              const float* weights, const float* refc) {
   float tf[9];
   compose_homography(inv_K, pose, row, col, depth, normal, tf);
+  census_corners(tf, np->radius, row, col);
   if (device_mix() != 0) return ncc_cost_device_mixed(st, np, tf, s, row, col, ref_sum, ref_sqsum, weights, refc, device_mix());
   const int n1d = (2 * np->radius) / np->step + 1;
   const int ntaps = n1d * n1d;
@@ -862,6 +959,7 @@ static float ncc_cost_device(const pmo_state* st, const ncc_params* np, const fl
   const float src_color_var = src_color_squared_sum - src_color_sum * src_color_sum;
   const float kMinVar = 1e-5f;
   const float kMaxCost = 2.0f;
+  census_ncc(ref_color_var, src_color_var);
   if (ref_color_var < kMinVar || src_color_var < kMinVar) return kMaxCost;
   const float covar = src_ref_color_sum - ref_sum * src_color_sum;
   const float var = sqrtf(ref_color_var * src_color_var);
@@ -892,6 +990,9 @@ static float geom_cost(const pmo_state* st, const float K4[4], const float inv_K
   float src_col = inv_forward_z * (P[0] * fp[0] + P[1] * fp[1] + P[2] * fp[2] + P[3]);
   float src_row = inv_forward_z * (P[4] * fp[0] + P[5] * fp[1] + P[6] * fp[2] + P[7]);
   const float src_depth = tex_src_depth(st, s, src_col + 0.5f, src_row + 0.5f);
+  CENSUS_IF(src_depth == 0.0f, PMC_SRC_DEPTH_ZERO);
+  CENSUS_IF(src_depth < 0.0f, PMC_SRC_DEPTH_NEGATIVE);
+  CENSUS_IF(!(fabsf(src_depth) <= FLT_MAX), PMC_SRC_DEPTH_NONFINITE);
   if (src_depth == 0.0f) return max_cost;
   src_col *= src_depth;
   src_row *= src_depth;
@@ -1104,6 +1205,8 @@ static void sweep_column(pmo_state* st, const pmo_options* opt, const sweep_opti
 
     /* :1047-1048 */
     prev_depth = propagate_depth(inv_K, prev_depth, prev_normal, (float)(row - 1), (float)row);
+    CENSUS_IF(prev_depth <= 0.0f, PMC_PROPAGATE_NONPOS);
+    CENSUS_IF(!(fabsf(prev_depth) <= FLT_MAX), PMC_PROPAGATE_NONFINITE);
 
     /* :1051-1052 */
     const float curr_depth = st->depth[(size_t)row * st->W + col];
@@ -1147,6 +1250,10 @@ static void sweep_column(pmo_state* st, const pmo_options* opt, const sweep_opti
         cum += prob;
         sampling_probs[i] = cum;
       }
+      CENSUS_IF(prob_sum == 0.0f, PMC_PROB_SUM_ZERO);
+      /* a NaN never leaves the running sum, so the last entry tells whether there is one */
+      CENSUS_IF(cum != cum, PMC_CDF_NAN);
+      CENSUS_IF(cum != cum && sampling_probs[0] == sampling_probs[0], PMC_CDF_NAN_AFTER_VALUE);
     }
 
     /* :1115-1126 */

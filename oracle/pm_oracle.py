@@ -75,6 +75,41 @@ def lib():
     return _lib
 
 
+# ---- census build: the same source with counters of the rarely taken paths (pm_oracle.c: PMO_CENSUS) ----------------
+# A second library, loaded only by the tests of the degenerate-input cases; lib() above, what smoke() and bench.py's
+# cpu_baseline use, never touches it.
+_CENSUS_LIB_PATH = os.path.join(_HERE, "libpm_oracle_census.so")
+CENSUS_FIELDS = ("taps", "tap_border", "tap_outside", "coord_saturated", "coord_nonfinite", "ncc_evals",
+                 "ncc_cut_ref_var", "ncc_cut_src_var", "ncc_src_var_nan", "ncc_ref_var_at_cut", "corner_div_nonpos", "prob_sum_zero",
+                 "cdf_nan", "cdf_nan_after_value", "src_depth_zero", "src_depth_negative", "src_depth_nonfinite",
+                 "propagate_nonpos", "propagate_nonfinite", "perturb_exhausted")
+_census_lib = None
+
+
+def census_lib():
+    global _census_lib
+    if _census_lib is None:
+        if not os.path.exists(_CENSUS_LIB_PATH) or (
+            os.path.getmtime(_CENSUS_LIB_PATH) < os.path.getmtime(os.path.join(_HERE, "pm_oracle.c"))
+        ):
+            subprocess.check_call(["make", "-C", _HERE, "libpm_oracle_census.so"], stdout=subprocess.DEVNULL)
+        _census_lib = C.CDLL(_CENSUS_LIB_PATH)
+        _census_lib.pmo_run.restype = C.c_int
+        _census_lib.pmo_census.restype = C.c_int
+        assert _census_lib.pmo_census(None, 0, 0) == len(CENSUS_FIELDS)
+    return _census_lib
+
+
+def run_census(options: Options, images, ref_idx: int, src_idxs, want_cost=False):
+    """run() through the census build: (outputs, {counter name: count of this solve})."""
+    L = census_lib()
+    L.pmo_census(None, 0, 1)
+    out = run(options, images, ref_idx, src_idxs, want_cost=want_cost, _lib=L)
+    counts = (C.c_uint64 * len(CENSUS_FIELDS))()
+    L.pmo_census(counts, len(CENSUS_FIELDS), 1)
+    return out, dict(zip(CENSUS_FIELDS, (int(c) for c in counts)))
+
+
 def default_options(**kw) -> Options:
     """PatchMatchOptions defaults (patch_match_options.h:37-126); sigma_spatial
     resolved to window_radius like PatchMatchController::ProcessProblem
@@ -131,9 +166,9 @@ def make_images(images):
     return arr, keep
 
 
-def run(options: Options, images, ref_idx: int, src_idxs, want_cost=False):
+def run(options: Options, images, ref_idx: int, src_idxs, want_cost=False, _lib=None):
     """Full PatchMatch solve on the CPU. Returns dict(depth, normal, sel_prob, mask[, cost])."""
-    L = lib()
+    L = _lib or lib()
     arr, keep = make_images(images)
     H, W = images[ref_idx]["gray"].shape
     S = len(src_idxs)

@@ -184,6 +184,28 @@ def test_host_side_cases_of_the_gpu_suite(pm_oracle):
     G.test_single_source_and_many_samples(pm_oracle)
 
 
+def _edge_case_params():
+    import pm_edge_cases as E
+    return E.case_family_pairs()
+
+
+@pytest.mark.parametrize("name,family", _edge_case_params())
+def test_edge_case(pm_oracle, request, name, family):
+    """The degenerate-input table of tests/pm_edge_cases.py through every kernel family, at the stand-in's shapes: what
+    the kernels' C++ does with borders, NaNs, the variance cut-off and non-positive divisors is settled here; what the
+    gfx950 instructions behind the restated helpers do with them, by the GPU test of the same name."""
+    G.check_edge_case(pm_oracle, request, name, family, small=True)
+
+
+def test_edge_batch_equals_single_runs(pm_oracle):
+    G.check_edge_batch(pm_oracle, small=True)
+
+
+@pytest.mark.parametrize("name", ["all_constant", "ring_360"])
+def test_edge_case_through_image_cache(pm_oracle, name):
+    G.check_edge_cached(pm_oracle, name, small=True)
+
+
 def test_committed_golden_fixture():
     """tests/golden/pm_48x36.npz (committed answer of the device-order oracle: one iteration + filter, every output map)
     reproduced by the product's kernels on the stand-in -- the GPU test of the same name, library swapped."""

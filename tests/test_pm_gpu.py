@@ -401,6 +401,99 @@ def test_cached_images_in_distant_slabs_are_rehomed(pm_oracle):
         L.pm_debug_set_image_slab_slots(C.c_size_t(0))
 
 
+# ---- degenerate inputs (tests/pm_edge_cases.py): border clamps, NaN / inf coordinates, the variance cut-off, non-positive
+# divisors, NaN CDFs, holes in the source depth maps -- every kernel family against the oracle, bit for bit ----
+
+def _edge_outputs(pm):
+    return dict(depth=pm.GetDepthMap(), normal=pm.GetNormalMap(), sel_prob=pm.GetSelProbMap(), cost=pm.GetCostMap(),
+                mask=pm.GetConsistencyMask())
+
+
+def check_edge_case(pm_oracle, request, name, family, small=False):
+    """One degenerate problem through one kernel family, bit for bit against the oracle; the handle must report the
+    family's kernel, so that a change of the dispatch cannot route a case away from it. Shared with the stand-in
+    (tests/test_pm_emul.py: small = True)."""
+    import pm_edge_cases as E
+    from colmap_amd import mvs
+    from switches import set_switch
+    switch, value, kernel = E.FAMILIES[family]
+    lib = mvs.lib()
+    if switch is not None:
+        set_switch(lib, switch, value)
+        request.addfinalizer(lambda: set_switch(lib, switch, None))
+    initial = family.endswith("_initial")
+    p = E.build(name, small)
+    _, h = E.paired_edge_options(pm_oracle, p, initial)
+    want = E.reference(pm_oracle, name, small, initial)
+    pm = mvs.PatchMatch(h, hip_problem(p.views, p.ref, p.src, p.maps))
+    try:
+        pm.Run()
+        E.assert_same_bits(want, _edge_outputs(pm), ("depth", "normal", "cost") if initial else E.ALL_MAPS)
+        assert pm.GetSweepKernelName() == kernel
+    finally:
+        pm.close()
+
+
+def _edge_case_params():
+    import pm_edge_cases as E
+    return E.case_family_pairs()
+
+
+@pytest.mark.parametrize("name,family", _edge_case_params())
+def test_edge_case(pm_oracle, request, name, family):
+    check_edge_case(pm_oracle, request, name, family)
+
+
+EDGE_BATCH = ("wide_depth_range", "all_constant", "one_constant_source")    # one shape: 48 x 36, S = 3
+
+
+def check_edge_batch(pm_oracle, small=False):
+    """pm_run_batch over three degenerate problems of one shape = the single runs' bits = the oracle's: the problem
+    that leads the batch (its CDFs hold NaNs, its planes are wild) shares launches and tables with its neighbours
+    and must leave nothing of itself in their results, in either position."""
+    import pm_edge_cases as E
+    from colmap_amd import mvs
+    for names in (EDGE_BATCH, EDGE_BATCH[::-1]):
+        pms = []
+        for name in names:
+            p = E.build(name, small)
+            _, h = E.paired_edge_options(pm_oracle, p)
+            pms.append(mvs.PatchMatch(h, hip_problem(p.views, p.ref, p.src, p.maps)))
+        mvs.run_batch(pms)
+        assert pms[0].GetLaunchShape()[0] == 3
+        for name, pm in zip(names, pms):
+            E.assert_same_bits(E.reference(pm_oracle, name, small), _edge_outputs(pm))
+            pm.close()
+
+
+def test_edge_batch_equals_single_runs(pm_oracle):
+    check_edge_batch(pm_oracle)
+
+
+def check_edge_cached(pm_oracle, name, small=False):
+    """pm_create_cached on a degenerate problem: gathers from the cache's packed copies give the uncached bits."""
+    import pm_edge_cases as E
+    from colmap_amd import mvs
+    p = E.build(name, small)
+    _, h = E.paired_edge_options(pm_oracle, p)
+    cache = mvs.ImageCache(0)
+    try:
+        for _ in range(2):      # the second problem finds every image in the cache
+            pm = mvs.PatchMatch(h, hip_problem(p.views, p.ref, p.src, p.maps), cache)
+            pm.Run()
+            E.assert_same_bits(E.reference(pm_oracle, name, small), _edge_outputs(pm))
+            pm.close()
+        st = cache.stats()
+        assert st["misses"] == len(p.src) and st["hits"] == len(p.src), st
+    finally:
+        cache.close()
+
+
+@pytest.mark.parametrize("name", ["all_constant", "ring_360"])
+def test_edge_case_through_image_cache(pm_oracle, name):
+    check_edge_cached(pm_oracle, name)
+
+
 def test_error_behaviour():
     from colmap_amd import mvs
     views = scene(3, 64, 48)
