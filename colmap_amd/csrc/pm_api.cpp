@@ -1,10 +1,13 @@
 // pm_api.cpp -- host side of the PatchMatch C ABI (include/colmap_amd_pm.h).
 //
 // Mirrors the host half of the reference's PatchMatchCuda
-// (src/colmap/mvs/patch_match_cuda.cu:1290-1939): option/problem validation,
-// uploads, pose tables for the four sweep directions, the sweep schedule. The
-// device half lives in pm_kernels.hip. Compiled with hipcc; no CPU fallback:
-// every entry point fails with an error if there is no usable HIP device.
+// (src/colmap/mvs/patch_match_cuda.cu:1290-1939) in two parts. What is decided -- option/problem validation, pose
+// tables for the four sweep directions, the shape of a run, the sweep schedule and its parameter blocks -- is plain
+// C++ in pm_host_plan.h (namespace pm_host). This file owns the device side of it: memory pools, the image cache,
+// uploads, streams, launches, the coalescing of concurrent runs; Create and RunBatchAsync build a plan, then do the
+// device work the plan states. Which kernels a run launches is decided by pm_plan_run (pm_kernels.hip), where the
+// device half lives. Compiled with hipcc; no CPU fallback: every entry point fails with an error if there is no
+// usable HIP device.
 #include "../../include/colmap_amd_pm.h"
 #include "pm_internal.h"
 
@@ -19,7 +22,6 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <set>
 #include <tuple>
 #include <stdexcept>
 #include <string>
@@ -31,14 +33,7 @@ namespace {
 
 thread_local std::string g_last_error;
 
-struct PmError : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-#define PM_CHECK(cond, msg)                                              \
-  do {                                                                   \
-    if (!(cond)) throw PmError(std::string("Check failed: ") + #cond + " " + (msg)); \
-  } while (0)
+using PmError = pm_host::Fail;  // what PM_CHECK (pm_host_plan.h) throws
 
 #define HIP_CALL(expr)                                                                  \
   do {                                                                                  \
@@ -145,138 +140,6 @@ struct DevBuf {
   ~DevBuf() { free(); }
 };
 
-// ---- host pose helpers (reference mvs/image.cc:97-150), float like the reference ----
-void Mat33Mul(const float A[9], const float B[9], float C[9]) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j)
-      C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-}
-
-void ComputeRelativePose(const float R1[9], const float T1[3], const float R2[9], const float T2[3],
-                         float R[9], float T[3]) {
-  float R1t[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) R1t[3 * i + j] = R1[3 * j + i];
-  Mat33Mul(R2, R1t, R);
-  for (int i = 0; i < 3; ++i)
-    T[i] = T2[i] - (R[3 * i] * T1[0] + R[3 * i + 1] * T1[1] + R[3 * i + 2] * T1[2]);
-}
-
-void ComposeProjectionMatrix(const float K[9], const float R[9], const float T[3], float P[12]) {
-  float RT[12];
-  for (int i = 0; i < 3; ++i) {
-    RT[4 * i] = R[3 * i];
-    RT[4 * i + 1] = R[3 * i + 1];
-    RT[4 * i + 2] = R[3 * i + 2];
-    RT[4 * i + 3] = T[i];
-  }
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 4; ++j)
-      P[4 * i + j] = K[3 * i] * RT[j] + K[3 * i + 1] * RT[4 + j] + K[3 * i + 2] * RT[8 + j];
-}
-
-void ComposeInverseProjectionMatrix(const float K[9], const float R[9], const float T[3],
-                                    float inv_P[12]) {
-  float m[16];
-  ComposeProjectionMatrix(K, R, T, m);
-  m[12] = m[13] = m[14] = 0.0f;
-  m[15] = 1.0f;
-  // explicit cofactor table (general 4x4 inverse), term order fixed so that the
-  // result is a deterministic function of m
-  float inv[16];
-  inv[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] + m[9] * m[7] * m[14] + m[13] * m[6] * m[11] - m[13] * m[7] * m[10];
-  inv[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] - m[8] * m[7] * m[14] - m[12] * m[6] * m[11] + m[12] * m[7] * m[10];
-  inv[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] + m[8] * m[7] * m[13] + m[12] * m[5] * m[11] - m[12] * m[7] * m[9];
-  inv[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] - m[8] * m[6] * m[13] - m[12] * m[5] * m[10] + m[12] * m[6] * m[9];
-  inv[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] - m[9] * m[3] * m[14] - m[13] * m[2] * m[11] + m[13] * m[3] * m[10];
-  inv[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] + m[8] * m[3] * m[14] + m[12] * m[2] * m[11] - m[12] * m[3] * m[10];
-  inv[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] - m[8] * m[3] * m[13] - m[12] * m[1] * m[11] + m[12] * m[3] * m[9];
-  inv[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] + m[5] * m[3] * m[14] + m[13] * m[2] * m[7] - m[13] * m[3] * m[6];
-  inv[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] - m[4] * m[3] * m[14] - m[12] * m[2] * m[7] + m[12] * m[3] * m[6];
-  inv[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] + m[4] * m[3] * m[13] + m[12] * m[1] * m[7] - m[12] * m[3] * m[5];
-  inv[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] - m[5] * m[3] * m[10] - m[9] * m[2] * m[7] + m[9] * m[3] * m[6];
-  inv[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] + m[4] * m[3] * m[10] + m[8] * m[2] * m[7] - m[8] * m[3] * m[6];
-  inv[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] - m[4] * m[3] * m[9] - m[8] * m[1] * m[7] + m[8] * m[3] * m[5];
-  const float det = m[0] * inv[0] + m[1] * inv[4] + m[2] * inv[8] + m[3] * inv[12];
-  const float inv_det = 1.0f / det;
-  for (int i = 0; i < 12; ++i) inv_P[i] = inv[i] * inv_det;
-}
-
-void ComputeProjectionCenter(const float R[9], const float T[3], float C[3]) {
-  for (int i = 0; i < 3; ++i) C[i] = -(R[i] * T[0] + R[3 + i] * T[1] + R[6 + i] * T[2]);
-}
-
-void RotatePose(const float RR[9], float R[9], float T[3]) {
-  float Rn[9], Tn[3];
-  Mat33Mul(RR, R, Rn);
-  for (int i = 0; i < 3; ++i) Tn[i] = RR[3 * i] * T[0] + RR[3 * i + 1] * T[1] + RR[3 * i + 2] * T[2];
-  std::memcpy(R, Rn, sizeof(Rn));
-  std::memcpy(T, Tn, sizeof(Tn));
-}
-
-void CheckOptions(const pm_options& o) {
-  // PatchMatchOptions::Check, reference mvs/patch_match_options.cc:73-100
-  if (o.depth_min != -1.0f || o.depth_max != -1.0f) {
-    PM_CHECK(o.depth_min <= o.depth_max, "depth_min <= depth_max");
-    PM_CHECK(o.depth_min >= 0.0, "depth_min >= 0");
-  }
-  PM_CHECK(o.window_radius <= 32, "window_radius <= kMaxPatchMatchWindowRadius");
-  PM_CHECK(o.sigma_color > 0.0, "");
-  PM_CHECK(o.window_radius > 0, "");
-  PM_CHECK(o.window_step > 0, "");
-  PM_CHECK(o.window_step <= 2, "");
-  PM_CHECK(o.num_samples > 0, "");
-  PM_CHECK(o.ncc_sigma > 0.0, "");
-  PM_CHECK(o.min_triangulation_angle >= 0.0, "");
-  PM_CHECK(o.min_triangulation_angle < 180.0, "");
-  PM_CHECK(o.incident_angle_sigma > 0.0, "");
-  PM_CHECK(o.num_iterations > 0, "");
-  PM_CHECK(o.geom_consistency_regularizer >= 0.0, "");
-  PM_CHECK(o.geom_consistency_max_cost >= 0.0, "");
-  PM_CHECK(o.filter_min_ncc >= -1.0, "");
-  PM_CHECK(o.filter_min_ncc <= 1.0, "");
-  PM_CHECK(o.filter_min_triangulation_angle >= 0.0, "");
-  PM_CHECK(o.filter_min_triangulation_angle <= 180.0, "");
-  PM_CHECK(o.filter_min_num_consistent >= 0, "");
-  PM_CHECK(o.filter_geom_consistency_max_cost >= 0.0, "");
-  // the reference's kernel dispatch only instantiates radius 1..20 (patch_match_cuda.cu:1313-1337)
-  PM_CHECK(o.window_radius <= 20, "window size not supported (reference instantiates radius 1..20)");
-  PM_CHECK(o.sigma_spatial > 0.0,
-           "sigma_spatial must be resolved by the caller (PatchMatchController sets it to "
-           "window_radius, patch_match.cc:436-438)");
-  PM_CHECK(o.depth_min > 0.0 && o.depth_max > 0.0,
-           "depth range must be set (PatchMatchController::ProcessProblem, patch_match.cc:425-434)");
-}
-
-void CheckProblem(const pm_options& o, const pm_problem& p) {
-  // PatchMatch::Check, reference mvs/patch_match.cc:67-126
-  PM_CHECK(o.gpu_index >= -1, "gpu_index >= -1");
-  PM_CHECK(p.images != nullptr, "problem.images");
-  PM_CHECK(p.num_src_images > 0, "src_image_idxs.size() > 0");
-  PM_CHECK(p.src_image_idxs != nullptr, "src_image_idxs");
-  std::set<int> unique(p.src_image_idxs, p.src_image_idxs + p.num_src_images);
-  unique.insert(p.ref_image_idx);
-  PM_CHECK((int)unique.size() == p.num_src_images + 1,
-           "duplicate source images or reference image used as source");
-  for (int idx : unique) {
-    PM_CHECK(idx >= 0, "image_idx >= 0");
-    PM_CHECK(idx < p.num_images, "image_idx < images.size()");
-    const pm_image& im = p.images[idx];
-    PM_CHECK(im.width > 0 && im.height > 0, "bitmap size");
-    PM_CHECK(im.gray != nullptr, "grey bitmap");
-    PM_CHECK(std::abs(im.K[1] - 0.0f) < 1e-6f, "K[1]");
-    PM_CHECK(std::abs(im.K[3] - 0.0f) < 1e-6f, "K[3]");
-    PM_CHECK(std::abs(im.K[6] - 0.0f) < 1e-6f, "K[6]");
-    PM_CHECK(std::abs(im.K[7] - 0.0f) < 1e-6f, "K[7]");
-    PM_CHECK(std::abs(im.K[8] - 1.0f) < 1e-6f, "K[8]");
-    if (o.geom_consistency) PM_CHECK(im.depth_map != nullptr, "depth map for geom_consistency");
-  }
-  if (o.geom_consistency) {
-    PM_CHECK(p.images[p.ref_image_idx].normal_map != nullptr, "reference normal map");
-    PM_CHECK(p.images[p.ref_image_idx].depth_map != nullptr, "reference depth map");
-  }
-}
-
 }  // namespace
 
 // Packed source images come out of slabs of equally sized slots (one hipMalloc per slab, at most 3.5 GB):
@@ -290,9 +153,6 @@ void CheckProblem(const pm_options& o, const pm_problem& p) {
 // with a few small images instead of > 4 GB of them.
 static size_t g_fp_slab_slots = 0;                 // 0: by image size (below)
 static std::atomic<unsigned long long> g_fp_rehomed{0};
-static inline uint64_t FpSpanLimit(size_t image_bytes) {
-  return g_fp_slab_slots ? (uint64_t)g_fp_slab_slots * image_bytes + 4097 : (1ull << 32);
-}
 
 class FpSlabPool {
  public:
@@ -467,9 +327,7 @@ struct pm_handle {
   hipStream_t stream = nullptr;
   int W = 0, H = 0, S = 0, src_w = 0, src_h = 0;
   std::vector<int> src_idxs;
-  // host pose tables
-  std::vector<float> poses_host;  // [4][S][43]
-  float ref_K[4][4], ref_inv_K[4][4];
+  pm_host::PoseTables tables;  // host pose tables
   // device buffers
   DevBuf<float> rec;
   std::vector<std::shared_ptr<FpEntry>> src_fp;  // per source image (possibly shared)
@@ -511,72 +369,29 @@ struct pm_handle {
 
 namespace {
 
-void BuildPoseTables(pm_handle* h, const pm_problem& prob) {
-  // InitTransforms, reference patch_match_cuda.cu:1694-1808
-  const pm_image& ref = prob.images[prob.ref_image_idx];
-  for (int i = 0; i < 4; ++i) {
-    h->ref_K[i][0] = ref.K[0];
-    h->ref_K[i][1] = ref.K[2];
-    h->ref_K[i][2] = ref.K[4];
-    h->ref_K[i][3] = ref.K[5];
-  }
-  std::swap(h->ref_K[1][0], h->ref_K[1][2]);
-  std::swap(h->ref_K[1][1], h->ref_K[1][3]);
-  h->ref_K[1][3] = h->W - 1 - h->ref_K[1][3];
-  h->ref_K[2][1] = h->W - 1 - h->ref_K[2][1];
-  h->ref_K[2][3] = h->H - 1 - h->ref_K[2][3];
-  std::swap(h->ref_K[3][0], h->ref_K[3][2]);
-  std::swap(h->ref_K[3][1], h->ref_K[3][3]);
-  h->ref_K[3][1] = h->H - 1 - h->ref_K[3][1];
-  for (int i = 0; i < 4; ++i) {
-    h->ref_inv_K[i][0] = 1.0f / h->ref_K[i][0];
-    h->ref_inv_K[i][1] = -h->ref_K[i][1] / h->ref_K[i][0];
-    h->ref_inv_K[i][2] = 1.0f / h->ref_K[i][2];
-    h->ref_inv_K[i][3] = -h->ref_K[i][3] / h->ref_K[i][2];
-  }
-  float rotated_R[9], rotated_T[3];
-  std::memcpy(rotated_R, ref.R, sizeof(rotated_R));
-  std::memcpy(rotated_T, ref.T, sizeof(rotated_T));
-  const float R_z90[9] = {0, 1, 0, -1, 0, 0, 0, 0, 1};
-  h->poses_host.assign((size_t)4 * h->S * kPoseStride, 0.0f);
-  for (int i = 0; i < 4; ++i) {
-    for (int s = 0; s < h->S; ++s) {
-      const pm_image& im = prob.images[h->src_idxs[s]];
-      float* p = h->poses_host.data() + ((size_t)i * h->S + s) * kPoseStride;
-      p[0] = im.K[0]; p[1] = im.K[2]; p[2] = im.K[4]; p[3] = im.K[5];
-      float rel_R[9], rel_T[3];
-      ComputeRelativePose(rotated_R, rotated_T, im.R, im.T, rel_R, rel_T);
-      std::memcpy(p + 4, rel_R, sizeof(rel_R));
-      std::memcpy(p + 13, rel_T, sizeof(rel_T));
-      ComputeProjectionCenter(rel_R, rel_T, p + 16);
-      ComposeProjectionMatrix(im.K, rel_R, rel_T, p + 19);
-      ComposeInverseProjectionMatrix(im.K, rel_R, rel_T, p + 31);
-    }
-    RotatePose(R_z90, rotated_R, rotated_T);
-  }
-}
-
 PmParams ParamsForSweep(const pm_handle* h, int rot) {
-  PmParams p = h->base;
-  p.rot = rot;
-  for (int k = 0; k < 4; ++k) {
-    p.refK[k] = h->ref_K[rot][k];
-    p.refInvK[k] = h->ref_inv_K[rot][k];
-  }
-  p.poses = h->poses.ptr + (size_t)rot * h->S * kPoseStride;
-  return p;
+  return pm_host::ParamsForSweep(h->base, h->tables, h->poses.ptr, rot);
 }
 
-// True when the packed images of `tab` can be read through one buffer resource (see Create).
-bool FpSpanFits(const std::vector<const uint32_t*>& tab, size_t fp_count) {
-  const uint32_t* lo = tab[0];
-  for (auto p : tab) lo = std::min(lo, p);
-  bool ok = ((uintptr_t)lo % 256) == 0;
-  for (auto p : tab) {
-    const uint64_t d = (uint64_t)((const char*)p - (const char*)lo);
-    ok = ok && d % 256 == 0 && d + fp_count * sizeof(uint32_t) + 4096 < FpSpanLimit(fp_count * sizeof(uint32_t));
+pm_host::RunKey RunKeyOf(const pm_handle* h) { return pm_host::MakeRunKey(h->device, h->base, h->opt); }
+
+int DeviceCUs(int device) {
+  static std::atomic<int> cus[16];
+  int ncu = cus[device & 15].load();
+  if (ncu == 0) {
+    HIP_CALL(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+    ncu = std::max(ncu, 1);
+    cus[device & 15] = ncu;
   }
-  return ok;
+  return ncu;
+}
+
+// Whether the packed images of `tab` can be read through one buffer resource, and as which slots of it.
+pm_host::FpSpan SpanOf(const std::vector<const uint32_t*>& tab, size_t fp_count) {
+  std::vector<uint64_t> addrs(tab.size());
+  for (size_t s = 0; s < tab.size(); ++s) addrs[s] = (uint64_t)(uintptr_t)tab[s];
+  return pm_host::PlanFpSpan(addrs.data(), (int)addrs.size(), fp_count,
+                             pm_host::FpSpanLimit(g_fp_slab_slots, fp_count * sizeof(uint32_t)));
 }
 
 void RehomeSourceImages(pm_handle* h, pm_image_cache* cache, const pm_problem& prob, size_t fp_count,
@@ -586,15 +401,8 @@ void RehomeSourceImages(pm_handle* h, pm_image_cache* cache, const pm_problem& p
   const int S = h->S;
   std::vector<const char*> slab(S);
   for (int s = 0; s < S; ++s) slab[s] = pool.SlabOf((*tab)[s]);
-  // candidates, best first: the slab with most of the problem's images, then the newest slab
-  std::map<const char*, int> votes;
-  for (int s = 0; s < S; ++s)
-    if (slab[s]) ++votes[slab[s]];
-  std::vector<std::pair<int, const char*>> cand;
-  for (auto& v : votes) cand.push_back({v.second, v.first});
-  std::sort(cand.begin(), cand.end(), [](auto& a, auto& b) { return a.first > b.first; });
   const char* newest = nullptr;
-  if (pool.FreeInNewest(bytes, &newest) > 0 && !votes.count(newest)) cand.push_back({0, newest});
+  if (pool.FreeInNewest(bytes, &newest) <= 0) newest = nullptr;
   auto try_slab = [&](const char* target) -> bool {
     std::vector<std::pair<int, uint32_t*>> moved;
     for (int s = 0; s < S; ++s) {
@@ -634,8 +442,8 @@ void RehomeSourceImages(pm_handle* h, pm_image_cache* cache, const pm_problem& p
     }
     return true;
   };
-  for (auto& c : cand)
-    if (try_slab(c.second)) return;
+  for (const char* c : pm_host::RehomeCandidates(slab, newest))
+    if (try_slab(c)) return;
   // every slab the problem touches is full: a fresh one (Take opens it when no slab has a free slot)
   uint32_t* probe = pool.Take(bytes);
   const char* fresh = pool.SlabOf(probe);
@@ -645,8 +453,8 @@ void RehomeSourceImages(pm_handle* h, pm_image_cache* cache, const pm_problem& p
 }
 
 void Create(const pm_options& opt_in, const pm_problem& prob, pm_image_cache* cache, pm_handle* h) {
-  CheckOptions(opt_in);
-  CheckProblem(opt_in, prob);
+  pm_host::CheckOptions(opt_in);
+  pm_host::CheckProblem(opt_in, prob);
   h->opt = opt_in;
   const pm_options& opt = h->opt;
 
@@ -731,35 +539,25 @@ void Create(const pm_options& opt_in, const pm_problem& prob, pm_image_cache* ca
       h->src_fp[s] = e;
       tab[s] = e->data.ptr;
     }
-    // One buffer resource per problem (below) needs the S images within 4 GB of each other. Images shared through
-    // the cache may sit in slabs that lie further apart (a long run packs more images than one slab holds): those of
-    // them outside the slab that holds most of the problem's images are then re-homed -- copied device to device into
-    // a free slot of that slab, the cache handed the new copy; problems that still use the old one keep it alive.
-    if (!FpSpanFits(tab, fp_count)) RehomeSourceImages(h, cache, prob, fp_count, &tab);
+    // One buffer resource per problem (pm_host::PlanFpSpan) needs the S images within 4 GB of each other. Images shared
+    // through the cache may sit in slabs that lie further apart (a long run packs more images than one slab holds):
+    // those of them outside the slab that holds most of the problem's images are then re-homed -- copied device to
+    // device into a free slot of that slab, the cache handed the new copy; problems that still use the old one keep it
+    // alive. Problems whose images still lie too far apart afterwards (separate allocations, shared through the image
+    // cache) take the explicit-index build of the kernels (fp_base = null).
+    pm_host::FpSpan span = SpanOf(tab, fp_count);
+    if (!span.fits) {
+      RehomeSourceImages(h, cache, prob, fp_count, &tab);
+      span = SpanOf(tab, fp_count);
+    }
+    h->fp_base = span.fits ? reinterpret_cast<const uint32_t*>((uintptr_t)span.base) : nullptr;
     h->src_fp_tab.alloc(S);
     HIP_CALL(hipMemcpyAsync(h->src_fp_tab.ptr, tab.data(), S * sizeof(const uint32_t*), hipMemcpyHostToDevice,
                             h->stream));
-    // The 11 x 11 sweep kernels read all S images through ONE buffer resource when they can (pm_kernels.hip:
-    // fp_resource): base = the lowest image address, an image = the slot (address - base) / kFpStrip in the offset
-    // register. The address unit forms the buffer offset in 32 bits, so every image must END within 4 GB of the
-    // base; problems whose images lie further apart (separate allocations, shared through the image cache) take
-    // the explicit-index build of the same kernels (fp_base = null).
-    {
-      const uint32_t* lo = tab[0];
-      for (int s = 0; s < S; ++s) lo = std::min(lo, tab[s]);
-      std::vector<uint32_t> offs(S);
-      bool ok = ((uintptr_t)lo % 256) == 0;
-      for (int s = 0; s < S; ++s) {
-        const uint64_t d = (uint64_t)((const char*)tab[s] - (const char*)lo);
-        ok = ok && d % 256 == 0 && d + fp_count * sizeof(uint32_t) + 4096 < FpSpanLimit(fp_count * sizeof(uint32_t));
-        offs[s] = (uint32_t)((d / kFpStrip) & 0xffffffffull);
-      }
-      h->src_fp_off.alloc(S);
-      HIP_CALL(hipMemcpyAsync(h->src_fp_off.ptr, offs.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-      HIP_CALL(hipStreamSynchronize(h->stream));  // `offs` dies with this scope
-      h->fp_base = ok ? lo : nullptr;
-    }
-    HIP_CALL(hipStreamSynchronize(h->stream));
+    h->src_fp_off.alloc(S);
+    HIP_CALL(hipMemcpyAsync(h->src_fp_off.ptr, span.offs.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice,
+                            h->stream));
+    HIP_CALL(hipStreamSynchronize(h->stream));  // `tab` and `span` die with this scope
   }
   if (opt.geom_consistency) {
     h->src_depth.alloc(slot * S);
@@ -788,50 +586,17 @@ void Create(const pm_options& opt_in, const pm_problem& prob, pm_image_cache* ca
   }
 
   // ---- InitTransforms -------------------------------------------------------------
-  BuildPoseTables(h, prob);
-  h->poses.alloc(h->poses_host.size());
-  HIP_CALL(hipMemcpyAsync(h->poses.ptr, h->poses_host.data(), h->poses_host.size() * sizeof(float),
+  h->tables = pm_host::BuildPoseTables(prob, W, H, h->src_idxs);
+  h->poses.alloc(h->tables.poses.size());
+  HIP_CALL(hipMemcpyAsync(h->poses.ptr, h->tables.poses.data(), h->tables.poses.size() * sizeof(float),
                           hipMemcpyHostToDevice, h->stream));
 
   // ---- InitWorkspaceMemory (reference :1810-1857) ---------------------------------
   PmParams& b = h->base;
-  std::memset(&b, 0, sizeof(b));
-  b.W = W; b.H = H; b.S = S; b.src_w = h->src_w; b.src_h = h->src_h;
-  b.fp_xmax = (float)(h->src_w + kFpRingX); b.fp_ymax = (float)(h->src_h + kFpRingY);
-  b.fp_rows1 = pm_fp_height(h->src_h) - 1;
-  b.radius = opt.window_radius;
-  b.step = opt.window_step;
-  b.ntap1d = (2 * b.radius) / b.step + 1;
-  b.ntaps = b.ntap1d * b.ntap1d;
-  b.num_samples = opt.num_samples;
-  b.rec_stride = 4 + 3 * S;
-  b.sel_out_off = 4 + S;       // sweep 0 writes half A ...
-  b.sel_in_off = 4 + 2 * S;    // ... and reads half B (= 0.5)
+  b = pm_host::ShapeParams(opt, W, H, S, h->src_w, h->src_h);
   b.C = pm_pick_columns(S, b.ntaps, b.num_samples, opt.geom_consistency != 0, b.radius,
                         opt.columns_per_group);
-  h->threads = opt.threads_per_group > 0 ? ((opt.threads_per_group + 63) / 64) * 64 : 128;
-  h->threads = std::min(h->threads, 256);  // pm_sweep_kernel __launch_bounds__
-  // SweepOptions (reference :1420-1438); doubles narrowed to float where the reference does
-  const float sigma_spatial = (float)opt.sigma_spatial;
-  const float sigma_color = (float)opt.sigma_color;
-  b.spatial_norm = 1.0f / (2.0f * sigma_spatial * sigma_spatial);
-  b.color_norm = 1.0f / (2.0f * sigma_color * sigma_color);
-  const float ncc_sigma = (float)opt.ncc_sigma;
-  const float min_tri = (float)(opt.min_triangulation_angle * 0.0174532925199432);
-  const float inc_sigma = (float)opt.incident_angle_sigma;
-  // LikelihoodComputer ctor (reference :700-707, 796-802)
-  b.cos_min_tri = std::cos(min_tri);
-  b.inv_inc_sigma_sq = -0.5f / (inc_sigma * inc_sigma);
-  b.inv_ncc_sigma_sq = -0.5f / (ncc_sigma * ncc_sigma);
-  b.ncc_norm = (float)(2.0f / (std::sqrt(2.0f * M_PI) * ncc_sigma *
-                               erff(2.0f / (ncc_sigma * 1.414213562f))));
-  b.geom_reg = (float)opt.geom_consistency_regularizer;
-  b.geom_max_cost = (float)opt.geom_consistency_max_cost;
-  b.filter_min_ncc = (float)opt.filter_min_ncc;
-  b.filter_cos_min_tri =
-      std::cos((float)(opt.filter_min_triangulation_angle * 0.0174532925199432));
-  b.filter_geom_max_cost = (float)opt.filter_geom_consistency_max_cost;
-  b.filter_min_num_consistent = opt.filter_min_num_consistent;
+  h->threads = pm_host::SweepThreads(opt.threads_per_group);
 
   h->rec.alloc((size_t)W * H * b.rec_stride);
   h->rng.alloc((size_t)W * H * kRngWords);
@@ -898,122 +663,60 @@ void RunBatchAsync(pm_handle** hs, int n, hipStream_t run_st = nullptr) {
   if (run_st) HIP_CALL(hipStreamSynchronize(h0->stream));  // create-time work of the leader (the others: below)
   const pm_options& opt = h0->opt;
   for (int b = 1; b < n; ++b) {
-    const pm_handle* h = hs[b];
-    PM_CHECK(h->device == h0->device, "batch on one device");
-    PM_CHECK(h->W == h0->W && h->H == h0->H && h->S == h0->S && h->src_w == h0->src_w &&
-                 h->src_h == h0->src_h,
-             "batched problems must have identical image sizes and source counts");
-    const pm_options& o = h->opt;
-    PM_CHECK(o.window_radius == opt.window_radius && o.window_step == opt.window_step &&
-                 o.num_samples == opt.num_samples && o.num_iterations == opt.num_iterations &&
-                 o.geom_consistency == opt.geom_consistency && o.filter == opt.filter &&
-                 o.max_sweeps == opt.max_sweeps,
+    // (a caller may batch profiled or traced problems, which no run gathers on its own: kRunDebug passes)
+    const pm_host::RunMismatch differ = pm_host::CompareRunKeys(RunKeyOf(h0), RunKeyOf(hs[b]));
+    PM_CHECK(differ != pm_host::kRunDevice, "batch on one device");
+    PM_CHECK(differ != pm_host::kRunSizes, "batched problems must have identical image sizes and source counts");
+    PM_CHECK(differ != pm_host::kRunOptions,
              "batched problems must share window / sample / iteration / filter options");
     // work enqueued on other streams at create time must be complete
-    HIP_CALL(hipStreamSynchronize(h->stream));
+    HIP_CALL(hipStreamSynchronize(hs[b]->stream));
   }
-  // Columns per wave by occupancy. A wave sweeps C columns top to bottom, so a launch has (problems x columns / C)
-  // waves for 16 wave slots per CU. C = 2 is the fastest shape when the GPU is full (pm_pick_columns), but ONE
-  // 2560 x 1920 problem -- how the reference's controller drives the seam, one problem per GPU thread
-  // (mvs/patch_match.cc:190-204) -- then has 960 .. 1 280 waves for 4 096 slots: with fewer than ~3/4 of the slots
-  // covered by everything alive on the device, one column per wave doubles the waves. The results do not depend
-  // on C (tests: group shapes); an explicit columns_per_group is respected.
-  // One launch geometry for the batch: the columns per wave of THIS run are a property of the run (every parameter
-  // block of the run carries it), never written back to a handle -- a handle re-run in another batch, or traced, sees
-  // its own shape again.
+  // One launch geometry for the batch (pm_host::PlanRunShape: columns per wave and helper wave by occupancy)
   const bool geom = opt.geom_consistency != 0;
-  int run_C = 64, run_help = 1;  // (64: pm_pick_columns never gives more)
-  {
-    // COLMAP_AMD_PM_COLS (experiments): columns per group for the handles that requested none
-    const int cols_switch = dev_switch_int("COLMAP_AMD_PM_COLS", 0);
-    bool automatic = h0->base.ntaps == 121;
-    for (int b = 0; b < n; ++b) {
-      const PmParams& s = hs[b]->base;
-      const bool requested = hs[b]->opt.columns_per_group > 0;
-      run_C = std::min(run_C, !requested && cols_switch > 0
-                                  ? pm_pick_columns(s.S, s.ntaps, s.num_samples, geom, s.radius, cols_switch) : s.C);
-      automatic = automatic && !requested;
-    }
-    if (automatic && cols_switch <= 0) {
-      static std::atomic<int> cus[16];
-      int ncu = cus[h0->device & 15].load();
-      if (ncu == 0) {
-        HIP_CALL(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h0->device));
-        ncu = std::max(ncu, 1);
-        cus[h0->device & 15] = ncu;
-      }
-      const long long slots = 16ll * ncu;
-      const int alive = std::max(n, g_live_handles[h0->device & 15].load());
-      const long long waves2 = (long long)alive * ((std::min(h0->W, h0->H) + 1) / 2);
-      // (images too small to fill the GPU either way keep the common shape: their time is launch latency)
-      const int C = (std::min(h0->W, h0->H) >= 512 && waves2 * 4 < slots * 3) ? 1 : 2;
-      run_C = std::min(run_C, C);
-      // ... and when even one wave per column leaves the GPU half empty (20 wave slots per CU for the photometric
-      // kernel; ONE 2560 x 1920 problem = 1 920 .. 2 560 waves for 5 120), a second wave per column shares the NCC
-      // rounds (pm_sweep_pair_kernel): bit-identical, test_group_shapes_do_not_change_results.
-      if (C == 1 && run_C == 1 && 2 * waves2 * 10 <= 20ll * ncu * 6) run_help = 2;
-    }
-    // COLMAP_AMD_PM_HELP (tests, A/B runs): 1 = never, 2 = always (one column per wave, any image size)
-    const int help_switch = dev_switch_int("COLMAP_AMD_PM_HELP", 0);
-    if (help_switch == 1) run_help = 1;
-    if (help_switch == 2 && h0->base.ntaps == 121) {
-      run_C = 1;
-      run_help = 2;
-    }
-  }
-  const int total_sweeps = opt.num_iterations * 4;
-  const int limit = opt.max_sweeps > 0 ? std::min(opt.max_sweeps, total_sweeps)
-                                       : (opt.max_sweeps < 0 ? 0 : total_sweeps);
-  // parameter blocks: [initial cost | sweep 0 | ... | sweep limit-1] x n problems
-  std::vector<PmParams> host((size_t)(limit + 1) * n);
+  const int cols_switch = dev_switch_int("COLMAP_AMD_PM_COLS", 0);
+  std::vector<pm_host::HandleColumns> cols(n);
   for (int b = 0; b < n; ++b) {
-    host[b] = ParamsForSweep(hs[b], 0);
-    host[b].C = run_C;
-    host[b].help = run_help;
+    const PmParams& s = hs[b]->base;
+    const bool requested = hs[b]->opt.columns_per_group > 0;
+    cols[b] = {!requested && cols_switch > 0 ? pm_pick_columns(s.S, s.ntaps, s.num_samples, geom, s.radius, cols_switch)
+                                             : s.C,
+               requested};
   }
-  const float total_num_steps = (float)total_sweeps;
-  // workgroup -> (problem, column group) mapping of a batched sweep launch (pm_sweep_kernel)
-  const int xcd_map_env = dev_switch_int("COLMAP_AMD_PM_XCD_MAP", 0);
-  const int xcd_map = (xcd_map_env == 1 && n % 8 == 0) ? 1 : (xcd_map_env == 2 ? 2 : 0);
-  int sel_out = h0->base.sel_out_off, sel_in = h0->base.sel_in_off;
+  const pm_host::RunShape run_shape =
+      pm_host::PlanRunShape(cols.data(), n, h0->base.ntaps, h0->W, h0->H, g_live_handles[h0->device & 15].load(),
+                            DeviceCUs(h0->device), cols_switch, dev_switch_int("COLMAP_AMD_PM_HELP", 0));
   // Which kernels the run launches, decided once. One kernel serves the whole batch: buffer-resource addressing only if
   // every problem's images allow it -- otherwise NO parameter block of the run carries a base.
+  PmParams shape = h0->base;
+  shape.C = run_shape.C;
+  shape.help = run_shape.help;
   bool fp_base_all = true;
   for (int b = 0; b < n; ++b) fp_base_all = fp_base_all && hs[b]->fp_base != nullptr;
-  const PmRunPlan run_plan = pm_plan_run(host[0], geom, h0->threads, fp_base_all, h0->base.prof != nullptr,
+  const PmRunPlan run_plan = pm_plan_run(shape, geom, h0->threads, fp_base_all, h0->base.prof != nullptr,
                                          h0->base.draws != nullptr);
-  if (!run_plan.fp_resource)
-    for (int b = 0; b < n; ++b) host[b].fp_base = nullptr;
-  for (int k = 0; k < limit; ++k) {
-    const int iter = k / 4, sweep = k % 4;
-    for (int b = 0; b < n; ++b) {
-      PmParams p = ParamsForSweep(hs[b], k % 4);
-      // exponentially reduce the perturbation, linearly increase the influence of the
-      // previous selection probabilities (reference :1446-1451)
-      p.perturbation = 1.0f / std::pow(2.0f, iter + sweep / 4.0f);
+  // parameter blocks: [initial cost | sweep 0 | ... | sweep limit-1] x n problems
+  const pm_host::SweepSchedule sched = pm_host::PlanSweeps(opt.num_iterations, opt.max_sweeps, opt.filter != 0, geom,
+                                                           h0->base.sel_out_off, h0->base.sel_in_off);
+  const int limit = (int)sched.sweeps.size();
+  std::vector<pm_host::RunProblem> probs(n);
+  for (int b = 0; b < n; ++b) probs[b] = {&hs[b]->base, &hs[b]->tables, hs[b]->poses.ptr};
+  std::vector<PmParams> host = pm_host::FillParamBlocks(sched, probs.data(), n, run_shape,
+                                                        dev_switch_int("COLMAP_AMD_PM_XCD_MAP", 0), run_plan.fp_resource);
 #ifdef COLMAP_AMD_DIAG_BUILD
-      {  // diagnostic only (results are garbage): fixed perturbation, to time a launch without far-flung random hypotheses
-        const double pert = dev_switch_double("COLMAP_AMD_PM_DIAG_PERT", -1.0);
-        if (pert >= 0.0) p.perturbation = (float)pert;
+  {  // diagnostics only (results are garbage): a fixed perturbation, to time a launch without far-flung random
+     // hypotheses, and the ablations of the sweep kernels
+    const double pert = dev_switch_double("COLMAP_AMD_PM_DIAG_PERT", -1.0);
+    const int ablate = dev_switch_int("COLMAP_AMD_PM_ABLATE", 0);
+    for (size_t i = n; i < host.size(); ++i) {
+      if (pert >= 0.0) {
+        host[i].perturbation = (float)pert;
+        host[i].perturbation_pi = (float)(host[i].perturbation * M_PI);
       }
-#endif
-      p.perturbation_pi = (float)(p.perturbation * M_PI);
-      p.prev_sel_prob_weight = (float)(iter * 4 + sweep) / total_num_steps;
-      p.sel_out_off = sel_out;
-      p.sel_in_off = sel_in;
-      p.xcd_map = xcd_map;
-      p.C = run_C;
-      p.help = run_help;
-#ifdef COLMAP_AMD_DIAG_BUILD
-      p.ablate = dev_switch_int("COLMAP_AMD_PM_ABLATE", 0);  // profiling builds only: results are garbage
-#else
-      p.ablate = 0;
-#endif
-      if (!run_plan.fp_resource) p.fp_base = nullptr;
-      host[(size_t)(k + 1) * n + b] = p;
+      host[i].ablate = ablate;
     }
-    std::swap(sel_out, sel_in);  // Rotate(): prev_sel_prob <- sel_prob (reference :1911-1915)
   }
+#endif
   h0->plan.alloc(host.size());
   HIP_CALL(hipMemcpyAsync(h0->plan.ptr, host.data(), host.size() * sizeof(PmParams),
                           hipMemcpyHostToDevice, st));
@@ -1030,22 +733,21 @@ void RunBatchAsync(pm_handle** hs, int n, hipStream_t run_st = nullptr) {
   }
   pm_launch_initial_cost(run_plan, h0->plan.ptr, n, st);
   for (int k = 0; k < limit; ++k) {
-    const bool last_sweep = k == total_sweeps - 1;
-    const bool fphoto = last_sweep && opt.filter;
-    const bool fgeom = last_sweep && opt.filter && geom;
+    const pm_host::Sweep& sweep = sched.sweeps[k];
     for (int b = 0; b < n; ++b)  // debug progress trace: every launch starts from an empty buffer
       if (hs[b]->trace.ptr)
         HIP_CALL(hipMemsetAsync(hs[b]->trace.ptr, 0, hs[b]->trace.count * sizeof(unsigned long long), st));
-    pm_launch_draws(run_plan, k % 4, h0->plan.ptr + (size_t)(k + 1) * n, n, st);
+    pm_launch_draws(run_plan, sweep.rot, h0->plan.ptr + (size_t)(k + 1) * n, n, st);
     HIP_CALL(hipEventRecord(h0->ev[2 * k], st));   // the events bracket the sweep kernel alone
-    pm_launch_sweep(run_plan, k % 4, h0->plan.ptr + (size_t)(k + 1) * n, n, fphoto, fgeom, st);
+    pm_launch_sweep(run_plan, sweep.rot, h0->plan.ptr + (size_t)(k + 1) * n, n, sweep.filter_photo, sweep.filter_geom,
+                    st);
     h0->sweep_kernel = run_plan.sweep_name;
     HIP_CALL(hipEventRecord(h0->ev[2 * k + 1], st));
   }
   for (int b = 0; b < n; ++b) {
     pm_handle* h = hs[b];
     h->sweeps_done = b == 0 ? limit : 0;
-    h->final_sel_off = sel_in;  // the half written by the last sweep
+    h->final_sel_off = sched.final_sel_off;  // the half written by the last sweep
     PmParams pe = ParamsForSweep(h, 0);
     pm_launch_extract(pe, h->final_sel_off, h->out_depth.ptr, h->out_normal.ptr, h->out_sel.ptr,
                       h->out_cost.ptr, st);
@@ -1061,8 +763,7 @@ void RunAsync(pm_handle* h) {
   h->launch_concurrency = 1;
 }
 
-// pm_run_batch: a batch of 16 or more problems runs as TWO sub-batches (whole multiples of eight images where the
-// count allows: a launch maps problem = workgroup id % batch, so eight problems sit on one XCD's L2 each) on the
+// pm_run_batch: a batch of 16 or more problems runs as TWO sub-batches (pm_host::FirstSubBatch) on the
 // streams of their first handles, enqueued back to back. A sweep launch ends with a drain -- the last of its column
 // groups finish one by one while the rest of the GPU idles, and the next sweep of the same images cannot start before
 // that -- but the problems of the other sub-batch do not depend on it: its launches fill the drain. Measured at
@@ -1088,8 +789,8 @@ hipStream_t SubBatchStream(int device, int k) {
 }
 
 void RunBatchSplitAsync(pm_handle** hs, int n) {
-  const bool split = n >= 16 && dev_switch_int("COLMAP_AMD_PM_BATCH_SPLIT", 1) != 0;
-  if (!split) {
+  const int first = pm_host::FirstSubBatch(n, dev_switch_int("COLMAP_AMD_PM_BATCH_SPLIT", 1));
+  if (first == n) {
     RunBatchAsync(hs, n);
     for (int b = 0; b < n; ++b) {
       hs[b]->launch_images = n;
@@ -1097,7 +798,6 @@ void RunBatchSplitAsync(pm_handle** hs, int n) {
     }
     return;
   }
-  const int first = std::min(n - 8, ((n / 2 + 7) / 8) * 8);
   RunBatchAsync(hs, first, SubBatchStream(hs[0]->device, 0));
   RunBatchAsync(hs + first, n - first, SubBatchStream(hs[0]->device, 1));
   for (int b = 0; b < n; ++b) {
@@ -1171,16 +871,6 @@ struct RunCoalescer {
 static RunCoalescer g_coalescer[16];
 static std::atomic<int> g_creating{0};   // pm_create calls in progress (any device)
 
-static bool BatchCompatible(const pm_handle* a, const pm_handle* b) {
-  const pm_options& x = a->opt;
-  const pm_options& y = b->opt;
-  return a->device == b->device && a->W == b->W && a->H == b->H && a->S == b->S && a->src_w == b->src_w &&
-         a->src_h == b->src_h && x.window_radius == y.window_radius && x.window_step == y.window_step &&
-         x.num_samples == y.num_samples && x.num_iterations == y.num_iterations &&
-         x.geom_consistency == y.geom_consistency && x.filter == y.filter && x.max_sweeps == y.max_sweeps &&
-         a->base.prof == nullptr && b->base.prof == nullptr && a->base.trace == nullptr && b->base.trace == nullptr;
-}
-
 void RunCoalesced(pm_handle* h) {
   if (dev_switch_int("COLMAP_AMD_PM_COALESCE", 1) == 0 || h->base.prof || h->base.trace) {
     RunAsync(h);
@@ -1214,7 +904,10 @@ void RunCoalesced(pm_handle* h) {
       }
     }
     std::vector<RunCall*> batch, rest;
-    for (RunCall* c : Q.pending) (BatchCompatible(Q.pending[0]->h, c->h) ? batch : rest).push_back(c);
+    for (RunCall* c : Q.pending) {
+      const bool together = pm_host::CompareRunKeys(RunKeyOf(Q.pending[0]->h), RunKeyOf(c->h)) == pm_host::kRunMatch;
+      (together ? batch : rest).push_back(c);
+    }
     Q.pending.swap(rest);
     lock.unlock();
     std::string err;
@@ -1273,8 +966,8 @@ void pm_options_init(pm_options* o) {
 int pm_check(const pm_options* options, const pm_problem* problem) {
   return Guard([&] {
     PM_CHECK(options && problem, "null argument");
-    CheckOptions(*options);
-    CheckProblem(*options, *problem);
+    pm_host::CheckOptions(*options);
+    pm_host::CheckProblem(*options, *problem);
   });
 }
 
@@ -1442,9 +1135,10 @@ int pm_get_ref_filter(pm_handle* h, uint8_t* image, float* sum, float* sqsum) {
 int pm_get_pose_tables(pm_handle* h, float* poses, float* ref_K, float* ref_inv_K) {
   return Guard([&] {
     PM_CHECK(h, "null");
-    if (poses) std::memcpy(poses, h->poses_host.data(), h->poses_host.size() * sizeof(float));
-    if (ref_K) std::memcpy(ref_K, h->ref_K, sizeof(h->ref_K));
-    if (ref_inv_K) std::memcpy(ref_inv_K, h->ref_inv_K, sizeof(h->ref_inv_K));
+    const pm_host::PoseTables& t = h->tables;
+    if (poses) std::memcpy(poses, t.poses.data(), t.poses.size() * sizeof(float));
+    if (ref_K) std::memcpy(ref_K, t.ref_K, sizeof(t.ref_K));
+    if (ref_inv_K) std::memcpy(ref_inv_K, t.ref_inv_K, sizeof(t.ref_inv_K));
   });
 }
 

@@ -31,7 +31,8 @@ def _emul_lib():
     global _LIB
     if _LIB is None:
         path = os.path.join(_HERE, "libpm_emul.so")
-        deps = [os.path.join(_CSRC, f) for f in ("pm_kernels.hip", "pm_api.cpp", "pm_internal.h")]
+        deps = [os.path.join(_CSRC, f) for f in ("pm_kernels.hip", "pm_api.cpp", "pm_internal.h",
+                                                      "pm_host_plan.h")]
         deps += [os.path.join(_HERE, "hip", "hip_runtime.h"), os.path.join(_HERE, "pm", "gfx950", "pm_gfx950_asm.h"),
                  os.path.join(_HERE, "pm", "pm_stubs.cpp"), os.path.join(_HERE, "build_pm.sh"),
                  os.path.join(os.path.dirname(_HERE), "..", "include", "colmap_amd_pm.h")]
