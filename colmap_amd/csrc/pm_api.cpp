@@ -1309,6 +1309,14 @@ unsigned long long pm_debug_set_image_slab_slots(size_t slots) {
   return g_fp_rehomed.load();
 }
 
+size_t pm_debug_wave_lds_bytes(int32_t num_sources, int32_t num_samples, int32_t columns, int32_t geom) {
+  return pm_quad_lds_bytes(num_sources, num_samples, columns, geom != 0);
+}
+
+int32_t pm_debug_pick_columns(int32_t num_sources, int32_t num_samples, int32_t geom) {
+  return pm_pick_columns(num_sources, 121, num_samples, geom != 0, 5, 0);
+}
+
 const char* pm_last_error(void) { return g_last_error.c_str(); }
 
 int pm_device_count(void) {

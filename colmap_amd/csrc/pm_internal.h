@@ -21,6 +21,8 @@ constexpr int kPmProfSlots = 24; // phase-profile counters per handle (pm_kernel
 __host__ __device__ inline int pm_draw_stride(int M) { return 4 + ((M + 3) & ~3); }
 // `requested` > 0: the caller's columns per group (PatchMatchOptions::columns_per_group or the development switch)
 int pm_pick_columns(int S, int ntaps, int num_samples, bool geom, int radius, int requested);
+// dynamic LDS bytes of a four-wave workgroup of the 11 x 11 wave kernels at C columns per wave (pm_debug_wave_lds_bytes)
+size_t pm_quad_lds_bytes(int S, int num_samples, int C, bool geom);
 
 // Which kernels a run launches, decided ONCE per run (pm_plan_run) from the common shape of its problems; the launchers
 // below only launch what the plan states. Two families, one arithmetic: the 11 x 11 wave kernels (quad; pair = a helper

@@ -739,7 +739,6 @@ struct Lds {
   lds_f32* ncc;     // [C][5][S] NCC per hypothesis/view, < 0: not computed (generic kernel)
   lds_f32* cost5;   // wave kernel: [C][5][S + 1] cost-map row (hypothesis 0), NCC of hypotheses 1..4; slot S of a row = 0
   lds_u32* drawn;   // wave kernel: [C][(S + 31) / 32] bitmap of the views drawn in this row
-  lds_u32* desc;    // wave kernel: [cap] pass-B descriptor per slot of the batch (run_tasks_wave)
   lds_f32* geo;     // [C][5][S] geometric cost (GEOM only)
   lds_f32* hyp;     // [C][5][4] depth, normal
   lds_f32* colf;    // [C][8] ref_sum, ref_sqsum, point[3], pad
@@ -749,16 +748,16 @@ struct Lds {
   lds_f32* csum;    // [C][5] accumulated hypothesis costs
   LDS_AS uint8_t* flags;  // [C][S] filter flags
   lds_u32* tasks;
-  lds_f32* th;      // [max_tasks][9] homography of each queued NCC task
+  lds_f32* th;      // [max_tasks][9] homography of each queued NCC task; wave kernel: [cap][kSlotWords] homography +
+                    // round record per position of the batch's pass-B order (batch_publish)
   lds_i32* ntasks;
   lds_f32* tapg;    // wave kernel: [4][128] tap tables (tap_tables_init)
   lds_u32* ring;    // wave kernel: [2][8][64] landing zone of the footprint gathers
-  LDS_AS uint8_t* tin;  // (unused: the wave kernel's Lds::desc lives at this offset)
 };
 
 struct LdsOffsets {
   uint32_t poses, fpb, tile, wgt, refc, fm, q, costv, betav, prevv, ncc, geo, hyp, colf, us, sv, best, csum,
-      flags, tasks, th, ntasks, tapg, ring, tin, total;
+      flags, tasks, th, ntasks, tapg, ring, total;
   uint32_t drawn = 0;
   uint32_t priv_stride = 0;  // multi-wave sweep kernel: bytes between the private regions of consecutive waves
 };
@@ -806,7 +805,6 @@ __host__ __device__ inline LdsOffsets lds_offsets(int C, int S, int radius, int 
   o.ntasks = take(16u);
   o.tapg = 0;
   o.ring = 0;
-  o.tin = 0;
   o.total = off;
   return o;
 }
@@ -835,7 +833,6 @@ __device__ __forceinline__ void lds_bind(Lds& L, lds_char* base, const LdsOffset
   L.ncc = (lds_f32*)(base + o.ncc);
   L.cost5 = (lds_f32*)(base + o.ncc);
   L.drawn = (lds_u32*)(base + o.drawn);
-  L.desc = (lds_u32*)(base + o.tin);
   L.geo = (lds_f32*)(base + o.geo);
   L.hyp = (lds_f32*)(base + o.hyp);
   L.colf = (lds_f32*)(base + o.colf);
@@ -849,7 +846,6 @@ __device__ __forceinline__ void lds_bind(Lds& L, lds_char* base, const LdsOffset
   L.ntasks = (lds_i32*)(base + o.ntasks);
   L.tapg = (lds_f32*)(base + o.tapg);
   L.ring = (lds_u32*)(base + o.ring);
-  L.tin = (LDS_AS uint8_t*)(base + o.tin);
 }
 
 __device__ __forceinline__ uint32_t task_pack(int c, int i, int s, int geom_only) {
@@ -1532,6 +1528,20 @@ constexpr int kQuadWaves = 4;   // waves per workgroup
 #endif
 constexpr int kQuadThCap = PM_QUAD_CAP;  // NCC task slots per batch (homographies in LDS)
 constexpr int kQuadOcc = PM_QUAD_OCC;    // workgroups per CU the photometric build is compiled for
+static_assert(kQuadThCap % 4 == 0 && kQuadThCap <= 64, "a batch is whole rounds of four tasks, one lane per task in pass A");
+// Words per position of a batch's pass-B order in Lds::th: the task's homography [0..8] (its three sums replace words
+// 0..2), then the round record [9]: the packed image as pass B adds it to the tap offset -- the buffer-resource slot, for
+// a position in an unclamped round with the offset of texel (0, 0) already in it -- with the task's column in the two
+// low bits (slots and that offset are multiples of 4: PlanFpSpan, fp_resource); explicit-index build: view | column << 16.
+// One word, not two: 40 bytes per position keep the four-wave block of the bench shape at 31 824 bytes = 25 LDS granules
+// of 1 280, the most that five workgroups per CU can have. (A second word with the weight row's offset ready-made, 44
+// bytes: 32 720 bytes = 26 granules, four workgroups per CU; sweep launches 472 ms against the parent's 444,
+// profiles/r07_bench_ab_44_byte_record/.) Pass B pays for the one word with an AND and a shift per round.
+constexpr int kSlotWords = 10;
+// Columns per wave of the 11 x 11 wave kernels: the record's two column bits. (8 before the round records; a caller
+// that asks for 5..8 columns per group now gets the generic family, same bits. Two columns are the default and the
+// fastest shape -- 604 / 643 / 718 ms per launch at C = 2 / 3 / 4 -- so nothing that is fast is lost.)
+constexpr int kWaveMaxColumns = 4;
 
 __device__ __forceinline__ uint32_t task16_pack(int c, int i, int s, int geom_only) {
   return ((uint32_t)c << 13) | ((uint32_t)geom_only << 12) | ((uint32_t)i << 9) | (uint32_t)s;
@@ -1584,9 +1594,8 @@ __host__ __device__ inline LdsOffsets lds_offsets_wave(int C, int S, int radius,
   o.drawn = take(4u * C * ((S + 31) / 32));   // bitmap of the views drawn in this row
   o.tasks = take(2u * max_tasks + (geom ? 2u * C * S : 0u));  // 16-bit task words: NCC tasks, then
                                                               // (GEOM) the geometric-cost-only list
-  o.th = take(36u * (uint32_t)cap);
+  o.th = take(4u * kSlotWords * (uint32_t)cap);  // homography + round record per position of the batch (batch_publish)
   o.ntasks = 0;
-  o.tin = take(4u * (uint32_t)cap);           // Lds::desc: pass-B descriptor per slot of the batch (inside-first order)
   o.priv_stride = off - shared;
   o.total = shared + (uint32_t)nw * o.priv_stride;
   return o;
@@ -1702,48 +1711,83 @@ __device__ __forceinline__ void wave_sync() {
   }
 }
 
+// Position of lane `tid`'s task in the batch's pass-B order: the tasks whose patch is inside the source image
+// (`m1`: their lanes) first, each class in lane order; `n` = lanes that hold a task.
+__device__ __forceinline__ int batch_position(unsigned long long m1, int n, int tid, bool inside) {
+  const unsigned long long valid = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
+  const unsigned long long m0 = valid & ~m1;
+  return inside ? lanes_below(m1) : __popcll(m1) + lanes_below(m0);
+}
+
+// End of pass A, lane per task: everything pass B needs to know about a task goes to the task's position in the
+// batch's order, in the form pass B consumes (kSlotWords). Order: the tasks whose patch is inside the source image
+// first. A round takes the cheaper unclamped addressing only when all four of its patches are inside; with the tasks
+// in list order one outside patch in four spoils the round, sorted they collect in the last rounds, and rounds
+// 0 .. n_inside / 4 - 1 are the unclamped ones: a scalar comparison in pass B. Results are stored per task, so the
+// order cannot change a bit. The batch is padded to whole rounds: lanes nb .. nb4 - 1 bring a copy of the batch's last
+// task with `inside` false, which lands behind every real task, is evaluated with clamped addresses and never stored.
+// Returns n_inside; `m1` = the lanes of the inside tasks (batch_position of the finishing lane).
+template <bool MUBUF>
+__device__ __forceinline__ int batch_publish(const PmParams& p, const Lds& L, int tid, int nb4, bool inside,
+                                             const float Hm[9], int c, int s, unsigned long long& m1) {
+  m1 = __ballot(inside ? 1 : 0);
+  const int n_inside = __popcll(m1);
+  if (tid < nb4) {
+    const int pos = batch_position(m1, nb4, tid, inside);
+    lds_f32* slot = L.th + pos * kSlotWords;
+    for (int k = 0; k < 9; ++k) slot[k] = Hm[k];
+    uint32_t img = (uint32_t)s | ((uint32_t)c << 16);
+    if (MUBUF) {
+      img = L.fpo[s] | (uint32_t)c;
+      // slot offset of texel (0, 0) relative to entry (0, 0): one strip (kFpRingX entries) and kFpRingY rows
+      if (pos < (n_inside & ~3)) img += 4u * ((uint32_t)p.fp_rows1 + 1u) + 4u * (uint32_t)kFpRingY;
+    }
+    ((lds_u32*)slot)[9] = img;
+  }
+  return n_inside;
+}
+
 // Mailbox of a wave pair (pm_sweep_pair_kernel): the words behind Lds::best[C] -- its 16-byte slot holds C <= 2 entries,
-// the pair kernel runs one column per group -- carry the size of the published batch and whether it is the phase's last.
+// the pair kernel runs one column per group -- carry the size of the published batch (nb | n_inside << 8) and whether
+// it is the phase's last.
 constexpr int kPairNb = 2, kPairLast = 3;
 
 // Pass B of a batch of NCC tasks, 16-lane group per task: one round = four tasks; all eight gathers of a lane are in
 // flight before the first texel is consumed (ncc_front / ncc_back). Control flow is wave-uniform -- every group runs
-// whole rounds, a group without a task in the last round recomputes the batch's last task and drops the result -- so
-// that the DPP rows are always fully active. A wave runs the rounds first, first + stride, ...: stride 1 normally;
-// with a helper wave (pm_sweep_pair_kernel) the two waves of a column group take alternate rounds, the helper the
-// batch's last one. The sums of a task replace its homography in L.th (slots are disjoint between rounds).
+// whole rounds, the batch is padded to whole rounds (batch_publish) -- so that the DPP rows are always fully active. A
+// wave runs the rounds first, first + stride, ...: stride 1 normally; with a helper wave (pm_sweep_pair_kernel) the two
+// waves of a column group take alternate rounds, the helper the batch's last one. Per round a lane reads ONE address
+// (its group's position, linear in the round) for homography and record; the sums of a task replace its homography.
 template <bool MUBUF>
 __device__ __forceinline__ void ncc_rounds_wave(const PmParams& p, const Lds& L, const v4i srd, const lds_f32* G, int tid,
-                                                int nb, int first, int stride) {
+                                                int nb, int n_inside, int first, int stride) {
   const int g = tid >> 4, j = tid & 15;
-  // slot offset of texel (0, 0) relative to entry (0, 0): one strip (kFpRingX entries) and kFpRingY rows
-  const uint32_t origin = 4u * ((uint32_t)p.fp_rows1 + 1u) + 4u * (uint32_t)kFpRingY;
-  const uint32_t gorigin = fp_index(kFpRingX, kFpRingY, (unsigned)p.fp_rows1);  // the same as an entry index
+  const uint32_t gorigin = fp_index(kFpRingX, kFpRingY, (unsigned)p.fp_rows1);  // texel (0, 0) as an entry index
   const int rounds = (nb + 3) >> 2;
-  for (int r = first; r < rounds; r += stride) {
-    const int tr = g + 4 * r;
-    const bool own = tr < nb;
-    const uint32_t d = L.desc[own ? tr : nb - 1];
-    // wave-uniform: the unclamped addressing only when all four patches of the round are inside
-    // (a recomputed task may already hold its sums instead of its homography: it must take the
-    // clamping path, where any coordinate is safe and the result is dropped)
-    const bool fast = __all(own && (d & 0x80u) != 0u) != 0;
-    const uint32_t slot = MUBUF ? L.fpo[d >> 16] : 0u;
-    gbl_u32* gbase = MUBUF ? nullptr : (gbl_u32*)L.fpb[d >> 16];
-    const lds_f32* H = L.th + (d & 63u) * 9u;
-    launder_lds(H);  // one address register for the nine reads (offsets 0..32) instead of a base + constant each
+  const int fast_rounds = n_inside >> 2;  // wave-uniform: the unclamped addressing when all four patches are inside
+  const lds_f32* H = L.th + (g + 4 * first) * kSlotWords;
+  const lds_f32* const end = L.th + nb * kSlotWords;
+  const lds_f32* wj = L.wgt + j;   // this lane's taps of column 0: one register each, whole (not a base + constant
+  const lds_f32* rj = L.refc + j;  // that every round would add again)
+  launder_lds(wj);
+  launder_lds(rj);
+  for (int r = first; r < rounds; r += stride, H += 4 * stride * kSlotWords) {
+    launder_lds(H);  // one address register for the ten reads (offsets 0..36) instead of a base + constant each
+    const uint32_t rec = ((const lds_u32*)H)[9];
+    const uint32_t img = rec & ~3u;
+    const uint32_t wofs = (MUBUF ? (rec & 3u) : (rec >> 16)) * (128u * 4u);  // the column's rows in Lds::wgt / refc
+    gbl_u32* gbase = MUBUF ? nullptr : (gbl_u32*)L.fpb[rec & 0xffffu];
     NccStage A;
     uint32_t tex[8];
-    if (fast) ncc_front<true, MUBUF>(p, srd, H, slot + origin, gbase + gorigin, G, j, A, tex);
-    else ncc_front<false, MUBUF>(p, srd, H, slot, gbase, G, j, A, tex);
+    if (r < fast_rounds) ncc_front<true, MUBUF>(p, srd, H, img, gbase + gorigin, G, j, A, tex);
+    else ncc_front<false, MUBUF>(p, srd, H, img, gbase, G, j, A, tex);
     __builtin_amdgcn_sched_barrier(0);
     TapRegs R;
-    const int c128 = (int)((d >> 8) & 0xffu) * 128;
-    tap_regs_load(R, L.wgt + c128, L.refc + c128, j);
+    tap_regs_load(R, (const lds_f32*)((const lds_char*)wj + wofs), (const lds_f32*)((const lds_char*)rj + wofs), 0);
     float s_sum, s_sq, s_ref;
     ncc_back(A, tex, R, j, s_sum, s_sq, s_ref);
-    if (j == 0 && own) {
-      lds_f32* Hw = L.th + (d & 63u) * 9u;
+    if (j == 0 && H < end) {  // (not the padding)
+      lds_f32* Hw = (lds_f32*)H;
       Hw[0] = s_sum;  // the homography of this task is no longer needed
       Hw[1] = s_sq;
       Hw[2] = s_ref;
@@ -1780,42 +1824,32 @@ __device__ __forceinline__ void run_tasks_wave(const PmParams& p, const Lds& L, 
   }
   for (int base = 0; base < n; base += CAP) {
     const int nb = min(CAP, n - base);
+    const int nb4 = (nb + 3) & ~3;  // whole rounds: lanes nb .. nb4 - 1 pad the batch with its last task
     PM_MARK("passA");
-    // pass A, lane per task: homography of the (hypothesis, view) pair (+ geometric cost)
+    // pass A, lane per task: homography of the (hypothesis, view) pair (+ geometric cost), round record
     bool inside = false;
-    uint32_t desc = 0;
-    if (tid < nb) {
-      const uint32_t task = tasks[base + tid];
-      const int c = task >> 13;
+    float Hm[9] = {};
+    int c = 0, s = 0;
+    if (tid < nb4) {
+      const uint32_t task = tasks[base + min(tid, nb - 1)];
+      c = task >> 13;
       const int i = (task >> 9) & 7;
-      const int s = task & 0x1ff;
+      s = task & 0x1ff;
       const lds_f32* h = L.hyp + (c * 5 + i) * 4;
       const lds_f32* pose = L.poses + s * L.pstride;
       const int col = col0 + c;
-      float Hm[9];
       compose_homography(p.refInvK, pose, row, col, h[0], h[1], h[2], h[3], Hm);
       centre_homography(Hm, row, col, p.radius);
-      for (int k = 0; k < 9; ++k) L.th[tid * 9 + k] = Hm[k];
-      inside = patch_inside(p, Hm);
-      desc = (uint32_t)tid | (inside ? 0x80u : 0u) | ((uint32_t)c << 8) | ((uint32_t)s << 16);
-      if (GEOM) L.geo[(c * 5 + i) * S1 + s] = geom_cost(p, pose, s, (float)row, (float)col, h[0]);
+      inside = tid < nb && patch_inside(p, Hm);
+      if (GEOM && tid < nb) L.geo[(c * 5 + i) * S1 + s] = geom_cost(p, pose, s, (float)row, (float)col, h[0]);
     }
-    {
-      // Order of the batch's tasks for pass B: the tasks whose patch is inside the source image first. A round
-      // takes the cheaper unclamped addressing only when all four of its patches are inside; with the tasks in
-      // list order one outside patch in four spoils the round, sorted they collect in the last rounds. Results
-      // are stored per task, so the order cannot change a bit. A slot's descriptor = everything pass B needs to
-      // know about its task: slot of the homography (bits 0-5), inside flag (7), column (8-15), view (16-).
-      const unsigned long long m1 = __ballot(inside ? 1 : 0);
-      const unsigned long long valid = nb >= 64 ? ~0ull : ((1ull << nb) - 1ull);
-      const unsigned long long m0 = valid & ~m1;
-      if (tid < nb) L.desc[inside ? lanes_below(m1) : __popcll(m1) + lanes_below(m0)] = desc;
-    }
+    unsigned long long m1;
+    const int n_inside = batch_publish<MUBUF>(p, L, tid, nb4, inside, Hm, c, s, m1);
     wave_sync<NW>();
     // pass B (ncc_rounds_wave); with a helper wave (HELP = 2, pm_sweep_pair_kernel) this wave takes every other round
     if (HELP > 1) {
       if (tid == 0) {
-        L.best[kPairNb] = nb;
+        L.best[kPairNb] = nb | (n_inside << 8);
         L.best[kPairLast] = base + CAP >= n ? 1 : 0;
       }
       __syncthreads();  // the batch is published: homographies, descriptors, its size
@@ -1824,7 +1858,7 @@ __device__ __forceinline__ void run_tasks_wave(const PmParams& p, const Lds& L, 
     PM_MARK("passB");
     {
       const int rounds = (nb + 3) >> 2;
-      ncc_rounds_wave<MUBUF>(p, L, srd, G, tid, nb, HELP > 1 ? (rounds & 1) : 0, HELP);
+      ncc_rounds_wave<MUBUF>(p, L, srd, G, tid, nb, n_inside, HELP > 1 ? (rounds & 1) : 0, HELP);
     }
     if (HELP > 1) __syncthreads();  // the helper's sums are in
     wave_sync<NW>();
@@ -1836,7 +1870,8 @@ __device__ __forceinline__ void run_tasks_wave(const PmParams& p, const Lds& L, 
       const int c = task >> 13;
       const int i = (task >> 9) & 7;
       const int s = task & 0x1ff;
-      L.cost5[(c * 5 + i) * S1 + s] = ncc_finish(L.th[tid * 9 + 0], L.th[tid * 9 + 1], L.th[tid * 9 + 2],
+      const lds_f32* sums = L.th + batch_position(m1, nb4, tid, ((m1 >> tid) & 1ull) != 0ull) * kSlotWords;
+      L.cost5[(c * 5 + i) * S1 + s] = ncc_finish(sums[0], sums[1], sums[2],
                                                  L.colf[c * 8 + 0], L.colf[c * 8 + 1], L.colf[c * 8 + 5]);
     }
     wave_sync<NW>();
@@ -1918,10 +1953,11 @@ __device__ __forceinline__ void sweep_wave_body(const PmParams* __restrict__ pp)
         int last;
         do {
           __syncthreads();
-          const int nb = L.best[kPairNb];
+          const int mail = L.best[kPairNb];
           last = L.best[kPairLast];
+          const int nb = mail & 0xff;
           const int rounds = (nb + 3) >> 2;
-          if (nb > 0) ncc_rounds_wave<MUBUF>(p, L, srd, L.tapg, tid, nb, (rounds - 1) & 1, HELP);
+          if (nb > 0) ncc_rounds_wave<MUBUF>(p, L, srd, L.tapg, tid, nb, mail >> 8, (rounds - 1) & 1, HELP);
           __syncthreads();
         } while (!last);
       }
@@ -2338,37 +2374,33 @@ __global__ void __launch_bounds__(64 * kQuadWaves, kQuadOcc) pm_initial_cost_wav
     patch_weight_sums(p, L, ncols, tid, 64);
     for (int base = 0; base < n; base += CAP) {
       const int nb = min(CAP, n - base);
-      // pass A, lane per (column, view): the homography of the pixel's initial plane
+      const int nb4 = (nb + 3) & ~3;  // whole rounds: lanes nb .. nb4 - 1 pad the batch with its last task
+      // pass A, lane per (column, view): the homography of the pixel's initial plane, round record
       bool inside = false;
-      uint32_t desc = 0;
-      if (tid < nb) {
-        const int t = base + tid;
-        const int c = t / S, sv = t - c * S;
+      float Hm[9] = {};
+      int c = 0, sv = 0;
+      if (tid < nb4) {
+        const int t = base + min(tid, nb - 1);
+        c = t / S;
+        sv = t - c * S;
         const int col = col0 + c;
         const float* rec = p.rec + (size_t)(row * p.W + col) * p.rec_stride;
-        float Hm[9];
         compose_homography(p.refInvK, L.poses + sv * L.pstride, row, col, rec[0], rec[1], rec[2], rec[3], Hm);
         centre_homography(Hm, row, col, p.radius);
-        for (int k = 0; k < 9; ++k) L.th[tid * 9 + k] = Hm[k];
-        inside = patch_inside(p, Hm);
-        desc = (uint32_t)tid | (inside ? 0x80u : 0u) | ((uint32_t)c << 8) | ((uint32_t)sv << 16);
+        inside = tid < nb && patch_inside(p, Hm);
       }
-      {
-        const unsigned long long m1 = __ballot(inside ? 1 : 0);
-        const unsigned long long valid = nb >= 64 ? ~0ull : ((1ull << nb) - 1ull);
-        const unsigned long long m0 = valid & ~m1;
-        if (tid < nb) L.desc[inside ? lanes_below(m1) : __popcll(m1) + lanes_below(m0)] = desc;
-      }
+      unsigned long long m1;
+      const int n_inside = batch_publish<MUBUF>(p, L, tid, nb4, inside, Hm, c, sv, m1);
       wave_sync<NW>();
-      ncc_rounds_wave<MUBUF>(p, L, srd, L.tapg, tid, nb, 0, 1);
+      ncc_rounds_wave<MUBUF>(p, L, srd, L.tapg, tid, nb, n_inside, 0, 1);
       wave_sync<NW>();
       if (tid < nb) {
         const int t = base + tid;
         const int c = t / S, sv = t - c * S;
         const int pix = row * p.W + col0 + c;
+        const lds_f32* sums = L.th + batch_position(m1, nb4, tid, ((m1 >> tid) & 1ull) != 0ull) * kSlotWords;
         p.rec[(size_t)pix * p.rec_stride + 4 + sv] =
-            ncc_finish(L.th[tid * 9 + 0], L.th[tid * 9 + 1], L.th[tid * 9 + 2], p.ref_sum[pix], p.ref_sqsum[pix],
-                       L.colf[c * 8 + 5]);
+            ncc_finish(sums[0], sums[1], sums[2], p.ref_sum[pix], p.ref_sqsum[pix], L.colf[c * 8 + 5]);
       }
       wave_sync<NW>();
     }
@@ -2487,8 +2519,12 @@ static size_t wave_lds_bytes(const PmParams& p, int C, bool geom, int nw) {
   return lds_offsets_wave(C, p.S, p.radius, p.ntaps, p.num_samples, geom, kQuadThCap, nw).total;
 }
 
+size_t pm_quad_lds_bytes(int S, int num_samples, int C, bool geom) {
+  return lds_offsets_wave(C, S, 5, 121, num_samples, geom, kQuadThCap, kQuadWaves).total;
+}
+
 bool PmRunPlan::wave_kernels_fit(const PmParams& p, int C, bool geom) {
-  return p.ntap1d == 11 && p.step >= 1 && p.S <= 512 && C <= 8 && wave_lds_bytes(p, C, geom, kQuadWaves) <= kQuadLdsBudget;
+  return p.ntap1d == 11 && p.step >= 1 && p.S <= 512 && C <= kWaveMaxColumns && wave_lds_bytes(p, C, geom, kQuadWaves) <= kQuadLdsBudget;
 }
 
 int pm_pick_columns(int S, int ntaps, int num_samples, bool geom, int radius, int requested) {
@@ -2512,8 +2548,8 @@ int pm_pick_columns(int S, int ntaps, int num_samples, bool geom, int radius, in
 //    buffer-resource addressing of the packed images (fp_resource); with it also as pm_sweep_pair_kernel (help = 2 at one
 //    column per wave) and, photometric sweeps, as pm_sweep_quad_prof_kernel (phase profile enabled);
 //  * pm_sweep_kernel / pm_initial_cost_kernel -- any window, workgroups with barriers (round 1's design), no phase
-//    profile: other window sizes, more source images than the four-wave LDS block holds, more than 8 columns per
-//    group, COLMAP_AMD_PM_WAVE=0 (tests: the A/B reference at the 11 x 11 window).
+//    profile: other window sizes, more source images than the four-wave LDS block holds, more than 4 columns per
+//    group (kWaveMaxColumns), COLMAP_AMD_PM_WAVE=0 (tests: the A/B reference at the 11 x 11 window).
 PmRunPlan pm_plan_run(const PmParams& p, bool geom, int threads, bool fp_base_all, bool profile, bool draws) {
   PmRunPlan plan;
   plan.geom = geom;

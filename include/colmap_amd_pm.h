@@ -215,6 +215,13 @@ void colmap_amd_set_switch(const char* name, const char* value);
  * `slots` images per slab, the span limit = one slab -- so that a handful of small images exercises that path; 0 =
  * the hardware's limits. Call before any image is packed. Returns the number of images re-homed so far. */
 unsigned long long pm_debug_set_image_slab_slots(size_t slots);
+/* Test hooks (no device call), for the default 11 x 11 window only (window_radius 5, window_step 1: the shape the
+ * wave kernels serve; other windows run the generic kernels, whose LDS block these do not describe): LDS bytes of one four-wave workgroup of the 11 x 11 sweep kernels for `num_sources`
+ * source images, `num_samples` view draws and `columns` columns per wave (five photometric workgroups share a CU up to
+ * 32 768 bytes each, four geometric ones up to 40 960), and the columns per wave a problem of that shape gets by
+ * default. */
+size_t pm_debug_wave_lds_bytes(int32_t num_sources, int32_t num_samples, int32_t columns, int32_t geom);
+int32_t pm_debug_pick_columns(int32_t num_sources, int32_t num_samples, int32_t geom);
 
 void pm_destroy(pm_handle* h);
 /* Device buffers of destroyed handles are kept (exact-size free lists, at most 64 GB and a quarter of the device's
