@@ -325,7 +325,7 @@ __device__ __forceinline__ bool walk_turn(const Params& p, const WalkTables& tb,
               const float nl0 = nl[0], nl1 = nl[1], nl2 = nl[2];
               // (qoff != goff: the pixel being expanded -- an image listed as its own neighbour -- is masked by the
               // mark issued a moment ago, which this load is not ordered behind)
-              if (qoff != goff && !masked_for(w, p.epoch, (unsigned)p.T, t) && d > 0.0f) {
+              if (qoff != goff && !masked_for(w, p.epoch, (unsigned)p.T, t) && !(d <= 0.0f)) {
                 float proj[3];
                 for (int r = 0; r < 3; ++r)
                   proj[r] = nx.P[4 * r] * ref[0] + nx.P[4 * r + 1] * ref[1] + nx.P[4 * r + 2] * ref[2] + nx.P[4 * r + 3] * 1.0f;
@@ -508,7 +508,7 @@ __device__ __forceinline__ int walk_turn_wide(const Params& p, const WalkTables&
             d = p.depth[qoff];
             const float* nl = p.normal + 3 * qoff;
             const float nl0 = nl[0], nl1 = nl[1], nl2 = nl[2];
-            if (qoff != goff && !masked_for(w, p.epoch, (unsigned)p.T, t) && d > 0.0f) {
+            if (qoff != goff && !masked_for(w, p.epoch, (unsigned)p.T, t) && !(d <= 0.0f)) {
               float proj[3];
               for (int r = 0; r < 3; ++r)
                 proj[r] = nx.P[4 * r] * ref[0] + nx.P[4 * r + 1] * ref[1] + nx.P[4 * r + 2] * ref[2] + nx.P[4 * r + 3] * 1.0f;
@@ -643,7 +643,7 @@ __global__ void __launch_bounds__(kWave) fusion_walk_kernel(Params p) {
       if (s >= 0) {
         const unsigned long long w = ld_word(p.word + img_off + (unsigned long long)s);
         d = p.depth[img_off + (unsigned long long)s];
-        cand = d > 0.0f && !masked_for(w, p.epoch, (unsigned)p.T, t);
+        cand = !(d <= 0.0f) && !masked_for(w, p.epoch, (unsigned)p.T, t);
       }
     }
     unsigned rs = ld_u32(&p.ctl->rstar[p.slot]);  // other waves lower it while this one runs: lane 0's view counts
@@ -715,7 +715,7 @@ __global__ void __launch_bounds__(kWave) fusion_walk_kernel(Params p) {
                   qd = p.depth[qoff];
                   const float* nl = p.normal + 3 * qoff;
                   const float nl0 = nl[0], nl1 = nl[1], nl2 = nl[2];
-                  if (qoff != goff && !masked_for(w, p.epoch, (unsigned)p.T, t) && qd > 0.0f) {
+                  if (qoff != goff && !masked_for(w, p.epoch, (unsigned)p.T, t) && !(qd <= 0.0f)) {
                     float proj[3];
                     for (int r = 0; r < 3; ++r)
                       proj[r] = nx.P[4 * r] * xyz[0] + nx.P[4 * r + 1] * xyz[1] + nx.P[4 * r + 2] * xyz[2] + nx.P[4 * r + 3] * 1.0f;

@@ -45,7 +45,8 @@ typedef struct fusion_options {
 
 /* One workspace image: mvs::Image pose at the MODEL image size, its colour bitmap, and the depth /
  * normal maps (Mat<float>, normal slice-major) at the depth-map size. used = 0 skips the image
- * (fusion.cc:204-213). mask: optional depth-map-sized bytes, non-zero = pre-masked pixel (:374-399). */
+ * (fusion.cc:204-213). mask: optional depth-map-sized bytes, non-zero = pre-masked pixel (:374-399).
+ * Non-finite depth or normal values are outside the contract (the reference has no defined result for them). */
 typedef struct fusion_image {
   int32_t width, height;
   float K[9], R[9], T[3];

@@ -23,7 +23,8 @@
 //           timing-dependent for T > 1, and so is this mode's). Not a checker of anything: it exists to TIME the
 //           reference's own multi-threaded path on the host's cores (bench.py cpu_baseline of the fusion leg).
 // All arithmetic float like the reference (Eigen::Vector3f / Matrix<float,3,4>), medians through
-// colmap::Percentile (math/math.h:205-224). Build: oracle/Makefile (-ffp-contract=off).
+// colmap::Percentile (math/math.h:205-224). Build: oracle/Makefile (-ffp-contract=off); with -DFUO_CENSUS a second
+// library that also counts how often the rarely taken paths run (below).
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -104,6 +105,58 @@ uint8_t TruncateCastU8(float v) {  // TruncateCast<float, uint8_t> (math/math.h)
 struct FusionData {
   int image_idx, row, col, traversal_depth;
 };
+
+// ---- census of the rarely taken paths -------------------------------------------------------------------------------
+// Compiled only with -DFUO_CENSUS, into a SECOND library (oracle/Makefile: libfusion_oracle_census.so) that only the
+// tests of the degenerate-input cases load (tests/fusion_edge_cases.py); in the plain build the macro expands to
+// nothing. The counters only observe: the census build returns the plain build's bits. They count over Fuse() (modes
+// 0 and 1) and Emit(); fuo_census() reads and clears them. Order = CENSUS_FIELDS in oracle/fusion_oracle.py.
+enum {
+  FUC_SEED_DEPTH_NONPOS,   // a turn's own pixel (not masked) has depth <= 0
+  FUC_NB_DEPTH_NONPOS,     // a pixel reached from a neighbour (not masked) has depth <= 0
+  FUC_DEPTH_SUBNORMAL,     // 0 < depth < FLT_MIN: positive, so the pixel is walked
+  FUC_PROJ_Z_NONPOS,       // a neighbour projection with third component <= 0
+  FUC_COORD_NONFINITE,     // a projected coordinate that is inf or NaN
+  FUC_COORD_TIE,           // fractional part exactly .5 before rounding
+  FUC_COORD_NEG_ZERO,      // in (-0.5, 0]: rounds to column / row 0 (from below: to -0.0)
+  FUC_COORD_FAR_EDGE,      // rounds to exactly width / height: rejected
+  FUC_DEPTH_ERR_AT_BAR,    // depth error == max_depth_error
+  FUC_REPROJ_AT_BAR,       // squared reprojection error == its bar
+  FUC_COS_AT_BAR,          // cosine == min_cos_normal_error
+  FUC_COS_ZERO_BELOW_BAR,  // cosine exactly 0 rejected (the float cos(90 degrees) is 6e-17, not 0)
+  FUC_SEED_OUT_OF_BOX,
+  FUC_NB_OUT_OF_BOX,
+  FUC_ON_BOX_FACE,         // a coordinate equal to a bounding-box face (inside)
+  FUC_SUPPORT_1,
+  FUC_SUPPORT_2,
+  FUC_SUPPORT_EVEN,
+  FUC_SUPPORT_ODD,
+  FUC_MEDIAN_TIE,          // a point / normal median whose middle order statistics are equal, or sit among equals
+  FUC_NORMAL_TOO_SHORT,    // norm < FLT_EPSILON
+  FUC_NORMAL_AT_EPSILON,   // norm == FLT_EPSILON: kept
+  FUC_COLOUR_TIE,          // colour median with fraction .5
+  FUC_COLOUR_OUTSIDE,      // bitmap lookup out of range
+  FUC_CAP_REACHED,         // max_num_pixels ended the walk
+  FUC_LEVEL_BOUND,         // max_traversal_depth stopped an expansion
+  FUC_BELOW_MIN_PIXELS,    // a non-empty support below min_num_pixels
+  FUC_COUNT
+};
+#ifdef FUO_CENSUS
+std::atomic<uint64_t> g_census[FUC_COUNT];
+#define CENSUS_IF(cond, i) do { if (cond) g_census[i].fetch_add(1, std::memory_order_relaxed); } while (0)
+inline bool CensusHalf(float q) { return std::isfinite(q) && std::fabs(q - std::trunc(q)) == 0.5f; }
+// the middle order statistics of a median's values are equal, or have an equal value next to them
+template <typename T>
+bool CensusMedianTie(std::vector<T> v) {
+  if (v.size() < 2) return false;
+  std::sort(v.begin(), v.end());
+  const size_t lo = (v.size() - 1) / 2, hi = v.size() / 2;  // lo == hi for an odd count (then >= 3 values)
+  if (lo != hi) return v[lo] == v[hi];
+  return v[lo - 1] == v[lo] || v[lo + 1] == v[lo];
+}
+#else
+#define CENSUS_IF(cond, i) ((void)0)
+#endif
 
 }  // namespace
 
@@ -264,6 +317,9 @@ struct Fuser {
       const size_t pix = (size_t)row * im.depth_width + col;
       if (mask[pix] > 0) continue;
       const float depth = im.depth_map[pix];
+      CENSUS_IF(depth <= 0.0f && depth_level == 0, FUC_SEED_DEPTH_NONPOS);
+      CENSUS_IF(depth <= 0.0f && depth_level > 0, FUC_NB_DEPTH_NONPOS);
+      CENSUS_IF(depth > 0.0f && depth < FLT_MIN, FUC_DEPTH_SUBNORMAL);
       if (depth <= 0.0f) continue;
       const float* Pi = &P[12 * (size_t)image_idx];
       if (depth_level > 0) {
@@ -272,10 +328,12 @@ struct Fuser {
           proj[r] = Pi[4 * r] * ref_point[0] + Pi[4 * r + 1] * ref_point[1] + Pi[4 * r + 2] * ref_point[2] +
                     Pi[4 * r + 3] * ref_point[3];
         const float depth_error = std::abs((proj[2] - depth) / depth);
+        CENSUS_IF(depth_error == opt.max_depth_error, FUC_DEPTH_ERR_AT_BAR);
         if (depth_error > opt.max_depth_error) continue;
         const float col_diff = proj[0] / proj[2] - col;
         const float row_diff = proj[1] / proj[2] - row;
         const float squared_reproj_error = col_diff * col_diff + row_diff * row_diff;
+        CENSUS_IF(squared_reproj_error == max_squared_reproj_error, FUC_REPROJ_AT_BAR);
         if (squared_reproj_error > max_squared_reproj_error) continue;
       }
       const size_t slice = (size_t)im.depth_width * im.depth_height;
@@ -285,6 +343,8 @@ struct Fuser {
       for (int r = 0; r < 3; ++r) normal[r] = iR[3 * r] * nl[0] + iR[3 * r + 1] * nl[1] + iR[3 * r + 2] * nl[2];
       if (depth_level > 0) {
         const float cos_normal_error = ref_normal[0] * normal[0] + ref_normal[1] * normal[1] + ref_normal[2] * normal[2];
+        CENSUS_IF(cos_normal_error == min_cos_normal_error, FUC_COS_AT_BAR);
+        CENSUS_IF(cos_normal_error == 0.0f && cos_normal_error < min_cos_normal_error, FUC_COS_ZERO_BELOW_BAR);
         if (cos_normal_error < min_cos_normal_error) continue;
       }
       const float* iP = &inv_P[12 * (size_t)image_idx];
@@ -299,13 +359,21 @@ struct Fuser {
         const int yy = static_cast<int>(std::round(static_cast<double>(row / scale[2 * image_idx + 1])));
         if (xx >= 0 && yy >= 0 && xx < im.bitmap_width && yy < im.bitmap_height)
           std::memcpy(color, im.rgb + 3 * ((size_t)yy * im.bitmap_width + xx), 3);
+        else
+          CENSUS_IF(true, FUC_COLOUR_OUTSIDE);
       }
       if (mode != 0 && mode != 3 && recorded >= kRecordCap) break;
       ++recorded;
       mask[pix] = 1;
       if (xyz[0] < opt.bbox_min[0] || xyz[1] < opt.bbox_min[1] || xyz[2] < opt.bbox_min[2] ||
-          xyz[0] > opt.bbox_max[0] || xyz[1] > opt.bbox_max[1] || xyz[2] > opt.bbox_max[2])
+          xyz[0] > opt.bbox_max[0] || xyz[1] > opt.bbox_max[1] || xyz[2] > opt.bbox_max[2]) {
+        CENSUS_IF(depth_level == 0, FUC_SEED_OUT_OF_BOX);
+        CENSUS_IF(depth_level > 0, FUC_NB_OUT_OF_BOX);
         continue;
+      }
+      CENSUS_IF(xyz[0] == opt.bbox_min[0] || xyz[1] == opt.bbox_min[1] || xyz[2] == opt.bbox_min[2] ||
+                    xyz[0] == opt.bbox_max[0] || xyz[1] == opt.bbox_max[1] || xyz[2] == opt.bbox_max[2],
+                FUC_ON_BOX_FACE);
       px.push_back(xyz[0]); py.push_back(xyz[1]); pz.push_back(xyz[2]);
       nx.push_back(normal[0]); ny.push_back(normal[1]); nz.push_back(normal[2]);
       cr.push_back(color[0]); cg.push_back(color[1]); cb.push_back(color[2]);
@@ -314,7 +382,9 @@ struct Fuser {
         ref_point[0] = xyz[0]; ref_point[1] = xyz[1]; ref_point[2] = xyz[2]; ref_point[3] = 1.0f;
         std::memcpy(ref_normal, normal, sizeof(normal));
       }
+      CENSUS_IF(px.size() >= max_pixels, FUC_CAP_REACHED);
       if (px.size() >= max_pixels) break;
+      CENSUS_IF(depth_level >= opt.max_traversal_depth - 1, FUC_LEVEL_BOUND);
       if (depth_level >= opt.max_traversal_depth - 1) continue;
       for (int k = optr[image_idx]; k < optr[image_idx + 1]; ++k) {
         const int next = oidx[k];
@@ -322,6 +392,17 @@ struct Fuser {
         const float* Pn = &P[12 * (size_t)next];
         float np[3];
         for (int r = 0; r < 3; ++r) np[r] = Pn[4 * r] * xyz[0] + Pn[4 * r + 1] * xyz[1] + Pn[4 * r + 2] * xyz[2] + Pn[4 * r + 3];
+#ifdef FUO_CENSUS
+        {
+          const float qc = np[0] / np[2], qr = np[1] / np[2];
+          const float wf = static_cast<float>(images[next].depth_width), hf = static_cast<float>(images[next].depth_height);
+          CENSUS_IF(np[2] <= 0.0f, FUC_PROJ_Z_NONPOS);
+          CENSUS_IF(!std::isfinite(qc) || !std::isfinite(qr), FUC_COORD_NONFINITE);
+          CENSUS_IF(CensusHalf(qc) || CensusHalf(qr), FUC_COORD_TIE);
+          CENSUS_IF((qc > -0.5f && qc <= 0.0f) || (qr > -0.5f && qr <= 0.0f), FUC_COORD_NEG_ZERO);
+          CENSUS_IF(std::round(qc) == wf || std::round(qr) == hf, FUC_COORD_FAR_EDGE);
+        }
+#endif
         int next_col, next_row;
         if (mode == 0 || mode == 3) {
           next_col = static_cast<int>(std::round(np[0] / np[2]));
@@ -349,16 +430,27 @@ struct Fuser {
   void Emit(std::vector<float>& px, std::vector<float>& py, std::vector<float>& pz, std::vector<float>& nx,
             std::vector<float>& ny, std::vector<float>& nz, std::vector<uint8_t>& cr, std::vector<uint8_t>& cg,
             std::vector<uint8_t>& cb, std::vector<int>& vis_order, fusion_result* dst) const {
+    CENSUS_IF(!px.empty() && px.size() < static_cast<size_t>(opt.min_num_pixels), FUC_BELOW_MIN_PIXELS);
     if (px.size() < static_cast<size_t>(opt.min_num_pixels) || px.empty()) return;
+    CENSUS_IF(px.size() == 1, FUC_SUPPORT_1);
+    CENSUS_IF(px.size() == 2, FUC_SUPPORT_2);
+    CENSUS_IF(px.size() % 2 == 0, FUC_SUPPORT_EVEN);
+    CENSUS_IF(px.size() % 2 == 1, FUC_SUPPORT_ODD);
+    CENSUS_IF(CensusMedianTie(px) || CensusMedianTie(py) || CensusMedianTie(pz) || CensusMedianTie(nx) ||
+                  CensusMedianTie(ny) || CensusMedianTie(nz),
+              FUC_MEDIAN_TIE);
     float fn[3] = {static_cast<float>(Median(nx)), static_cast<float>(Median(ny)), static_cast<float>(Median(nz))};
     const float norm = std::sqrt(fn[0] * fn[0] + fn[1] * fn[1] + fn[2] * fn[2]);
+    CENSUS_IF(norm < FLT_EPSILON, FUC_NORMAL_TOO_SHORT);
+    CENSUS_IF(norm == FLT_EPSILON, FUC_NORMAL_AT_EPSILON);
     if (norm < FLT_EPSILON) return;
     const float pt[6] = {static_cast<float>(Median(px)), static_cast<float>(Median(py)), static_cast<float>(Median(pz)),
                          fn[0] / norm, fn[1] / norm, fn[2] / norm};
     dst->xyz_normal.insert(dst->xyz_normal.end(), pt, pt + 6);
-    dst->rgb.push_back(TruncateCastU8(std::round(static_cast<float>(Median(cr)))));
-    dst->rgb.push_back(TruncateCastU8(std::round(static_cast<float>(Median(cg)))));
-    dst->rgb.push_back(TruncateCastU8(std::round(static_cast<float>(Median(cb)))));
+    const float fc[3] = {static_cast<float>(Median(cr)), static_cast<float>(Median(cg)), static_cast<float>(Median(cb))};
+    CENSUS_IF(fc[0] - std::floor(fc[0]) == 0.5f || fc[1] - std::floor(fc[1]) == 0.5f || fc[2] - std::floor(fc[2]) == 0.5f,
+              FUC_COLOUR_TIE);
+    for (int ch = 0; ch < 3; ++ch) dst->rgb.push_back(TruncateCastU8(std::round(fc[ch])));
     // the reference copies a FlatHashSet (unspecified order); here: sorted image indices
     std::sort(vis_order.begin(), vis_order.end());
     dst->vis_idx.insert(dst->vis_idx.end(), vis_order.begin(), vis_order.end());
@@ -759,5 +851,16 @@ FUO_API void fuo_last_schedule(long long* discarded, long long* conflicts, long 
 }
 
 FUO_API const char* fuo_last_error(void) { return g_error.c_str(); }
+
+#ifdef FUO_CENSUS
+// the counters since the last clearing: out[0 .. min(n, count)), cleared if `reset`; returns their number
+FUO_API int fuo_census(uint64_t* out, int n, int reset) {
+  for (int i = 0; i < FUC_COUNT; ++i) {
+    if (out && i < n) out[i] = g_census[i].load(std::memory_order_relaxed);
+    if (reset) g_census[i].store(0, std::memory_order_relaxed);
+  }
+  return FUC_COUNT;
+}
+#endif
 
 }  // extern "C"

@@ -6,12 +6,14 @@ float32 restatement; mode 1 (the same walk, turns in the order of the reference'
 mvs/fusion.cc:253-269: stripes of ten rows, its threads advancing in step) against the ground truth of the
 synthetic renderer and mode 0; mode 2 (a simulation of how the HIP kernels execute that order: speculative
 passes, tentative marks, rank cut) against mode 1. GPU tests: colmap_amd/csrc/fusion.hip through fusion_run
-equals mode 1 bit for bit. tests/test_fusion_emul.py runs the same kernels on the CPU."""
+equals mode 1 bit for bit. tests/test_fusion_emul.py runs the same kernels on the CPU. The degenerate inputs of
+tests/fusion_edge_cases.py (what each reaches: tests/fusion_edge_cases.md) go through all of them."""
 import os
 
 import numpy as np
 import pytest
 
+import fusion_edge_cases as E
 import fusion_oracle
 from colmap_amd import fusion, mvs, workspace as W
 from pm_common import scene, write_dense_workspace
@@ -44,6 +46,9 @@ def _fuse_reference(opt, images, overlap):
     n = len(images)
     P, iP, iR, masks = [], [], [], []
     for im in images:
+        if not im.used:     # fusion.cc:204-213: never touched again
+            P.append(None); iP.append(None); iR.append(None); masks.append(None)
+            continue
         K = np.asarray(im.K, f32).reshape(3, 3).copy()
         R = np.asarray(im.R, f32).reshape(3, 3)
         T = np.asarray(im.T, f32).reshape(3)
@@ -158,9 +163,10 @@ def _fuse_reference(opt, images, overlap):
     while idx >= 0:
         if used[idx]:
             dh, dw = images[idx].depth_map.shape
-            for r in range(dh):
-                for c in range(dw):
-                    fuse_pixel(idx, r, c)
+            with np.errstate(all="ignore"):   # a subnormal depth overflows the relative depth error, as in the reference
+                for r in range(dh):
+                    for c in range(dw):
+                        fuse_pixel(idx, r, c)
         fused[idx] = True
         nxt = -1
         for j in overlap[idx]:
@@ -290,6 +296,51 @@ def _options_masks_and_bounding_box(fuse):
 
 
 # ------------------------------------------------------------------------------------------------
+# the checker on degenerate inputs (tests/fusion_edge_cases.py)
+# ------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", list(E.CASES))
+def test_edge_case_sequential_oracle_equals_python_restatement(name):
+    """mode 0 against the float32 restatement written from the reference's text, on inputs where the side a pixel
+    falls on is decided at exact equality, at a rounding tie or by the sign of a zero."""
+    opt, images, overlap = E.build(name)
+    got = E.reference(fusion_oracle, name, mode=0)
+    wp, wn, wc, wv = _fuse_reference(opt, images, overlap)
+    want = fusion.FusedPoints(wp, wn, wc, [np.array(v, np.int32) for v in wv])
+    assert len(wp) > 0 and not np.isnan(wp).any() and not np.isnan(wn).any()
+    E.assert_same(want, got, name)
+
+
+@pytest.mark.parametrize("name", list(E.CASES))
+def test_edge_case_schedules_agree(name):
+    """The simulation of the kernels' passes (mode 2) equals the sequential turns in pool order (mode 1), and with one
+    pool thread that order is the row-major one of mode 0."""
+    want = E.reference(fusion_oracle, name)
+    assert len(want.xyz) > 0
+    E.assert_same(want, fusion_oracle.fuse(*E.build(name), mode=2), name)
+    E.assert_same(E.reference(fusion_oracle, name, mode=0, num_threads=1), E.reference(fusion_oracle, name, num_threads=1), name)
+
+
+@pytest.mark.parametrize("name", list(E.CASES))
+def test_edge_case_reaches_the_paths_it_is_named_for(name):
+    """The census build (fusion_oracle.cpp: FUO_CENSUS) counts, over the mode-1 solve of the case, how often the paths the
+    case exists for were taken: every counter the case names clears its floor (a bit-exact pass on a case that never
+    leaves the happy path would prove nothing). The census build returns the plain build's bits."""
+    out, counts = fusion_oracle.fuse_census(*E.build(name), mode=1)
+    print(name, {k: v for k, v in counts.items() if v})
+    for counter, floor in E.CASES[name].counters.items():
+        assert counts[counter] >= floor, (counter, counts[counter], floor)
+    E.assert_same(E.reference(fusion_oracle, name), out, name)
+
+
+def test_fusion_census_covers_every_counter():
+    """Every counter of the census is named, with a floor, by at least one case: none is dead under the table."""
+    named = set().union(*(c.counters for c in E.CASES.values()))
+    assert named <= set(fusion_oracle.CENSUS_FIELDS)
+    assert named == set(fusion_oracle.CENSUS_FIELDS), set(fusion_oracle.CENSUS_FIELDS) - named
+
+
+# ------------------------------------------------------------------------------------------------
 # the HIP path against the checker (bit for bit)
 # ------------------------------------------------------------------------------------------------
 
@@ -337,6 +388,26 @@ def test_hip_fusion_equals_parallel_oracle(name):
     assert len(want.xyz) > 20
     assert _same(got, want), (len(got.xyz), len(want.xyz))
     assert _same(fusion.fuse(opt, images, overlap), got)  # marks and ranks decide, not timing
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(E.CASES))
+def test_hip_fusion_equals_oracle_on_degenerate_inputs(name):
+    """The kernels against the checker where the result hinges on a comparison at exact equality, on roundf at a tie, on
+    a subnormal or negative-zero depth, on a median among equals: points, normals, colours and visibility of mode 1;
+    the same from a second run; the row-major mode 0 with one pool thread; mode 1 again from the depth-first walks."""
+    from colmap_amd._lib import lib
+    from switches import switches
+    opt, images, overlap = E.build(name)
+    want = E.reference(fusion_oracle, name)
+    assert len(want.xyz) > 0
+    got = fusion.fuse(opt, images, overlap)
+    E.assert_same(want, got, name)
+    E.assert_same(got, fusion.fuse(opt, images, overlap), name + " (second run)")
+    one = E.build(name, num_threads=1)
+    E.assert_same(E.reference(fusion_oracle, name, mode=0, num_threads=1), fusion.fuse(*one), name + " (one thread)")
+    with switches(lib(), COLMAP_AMD_FUSION_WIDE=0):
+        E.assert_same(want, fusion.fuse(opt, images, overlap), name + " (depth-first)")
 
 
 @pytest.mark.gpu

@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import fusion_edge_cases as E
 import fusion_oracle
 from colmap_amd import fusion
 from pm_common import scene
@@ -84,6 +85,15 @@ def test_emulated_kernel_equals_oracle_on_the_gpu_test_inputs(emul, name):
     want = fusion_oracle.fuse(opt, images, overlap, mode=1)
     got = fusion.fuse(opt, images, overlap, entry_points=emul)
     assert len(want.xyz) > 20 and _same(got, want), (len(got.xyz), len(want.xyz))
+
+
+@pytest.mark.parametrize("name", list(E.CASES))
+def test_emulated_kernel_equals_oracle_on_degenerate_inputs(emul, name):
+    """tests/fusion_edge_cases.py through the product's capacities: comparisons at exact equality, rounding ties, depth
+    signs, medians among equals, as host arithmetic (what the GPU makes of them: tests/test_fusion.py -m gpu)."""
+    want = E.reference(fusion_oracle, name)
+    assert len(want.xyz) > 0
+    E.assert_same(want, fusion.fuse(*E.build(name), entry_points=emul), name)
 
 
 def _schedule():
