@@ -1206,6 +1206,187 @@ __device__ __forceinline__ void ncc_back(const NccStage& st, const uint32_t tex[
 #define PM_MARK(name)
 #endif
 
+// ---------------------------------------------------------------------------
+// The row-step phases both families run (pm_sweep_kernel below; sweep_wave_body, 11 x 11), stated once, per item or per
+// column. The kernels keep their loops, item -> (column, view) division and synchronisation, and pass in what they hoist
+// out of the row loop (iK, S) and what differs between them: no function here knows its caller. The source of P1's
+// random numbers, P3b, P3c, P5a, P5c and the NCC task runners differ on purpose and stay in the kernels.
+// ---------------------------------------------------------------------------
+
+// Backward messages of one (column, view) for rows first_row .. 0 (:976-989), to sel_out; forward messages start at 0.5.
+__device__ __forceinline__ void backward_messages(const PmParams& p, const Lds& L, int col0, int c, int s, int S,
+                                                  int first_row) {
+  float beta = 0.5f;
+  for (int row = first_row; row >= 0; --row) {
+    float* rec = p.rec + (size_t)pix_index(p, row, col0 + c) * p.rec_stride;
+    beta = hmm_message<false>(p, rec[4 + s], beta);
+    rec[p.sel_out_off + s] = beta;
+  }
+  L.fm[c * S + s] = 0.5f;
+}
+
+// Per-column state kept across rows: the previous row's plane, before row 0 the column's own (:1022-1028).
+__device__ __forceinline__ void column_init(const PmParams& p, const Lds& L, int col0, int c) {
+  const float* rec = p.rec + (size_t)pix_index(p, 0, col0 + c) * p.rec_stride;
+  float sx, sy;
+  normal_to_sweep(p.rot, rec[1], rec[2], sx, sy);
+  lds_f32* h1 = L.hyp + (c * 5 + 1) * 4;
+  h1[0] = rec[0]; h1[1] = sx; h1[2] = sy; h1[3] = rec[3];
+}
+
+// The random numbers of a column's row from the pixel's plane as stored, in the reference's order of its stream: perturbed
+// depth and normal (:1055-1062) to r[0 .. 3], then the M uniforms of the view draws (:1129) to u[0 .. M - 1].
+template <typename RPtr, typename UPtr>
+__device__ __forceinline__ void draw_row(const PmParams& p, const float* iK, int row, int col, int M, float cd, float nx,
+                                         float ny, float cn2, Rng& rng, RPtr r, UPtr u) {
+  float cn0, cn1;
+  normal_to_sweep(p.rot, nx, ny, cn0, cn1);
+  const float dmin = (1.0f - p.perturbation) * cd;
+  const float dmax = (1.0f + p.perturbation) * cd;
+  const float rd = rng_uniform(rng) * (dmax - dmin) + dmin;
+  float rn0, rn1, rn2;
+  perturb_normal(iK, row, col, p.perturbation_pi, cn0, cn1, cn2, rng, rn0, rn1, rn2);
+  r[0] = rd; r[1] = rn0; r[2] = rn1; r[3] = rn2;
+  for (int m = 0; m < M; ++m) u[m] = rng_uniform(rng) - FLT_EPSILON;
+}
+
+// P1, lane per column: the row's hypotheses -- the pixel's current plane, the previous row's propagated to this row
+// (:1047-1052), the random plane r[0 .. 3] (draw_row) and its two mixtures with the current one -- and the point at the
+// current depth (ComputePointAtDepth, :1067-1068).
+template <typename RPtr>
+__device__ __forceinline__ void row_hypotheses(const PmParams& p, const Lds& L, const float* iK, int row, int col0,
+                                               int c, RPtr r) {
+  const int col = col0 + c;
+  const int pix = pix_index(p, row, col);
+  const float* rec = p.rec + (size_t)pix * p.rec_stride;
+  lds_f32* h = L.hyp + c * 20;
+  h[4] = propagate_depth(iK, h[4], h[6], h[7], (float)(row - 1), (float)row);
+  const float cd = rec[0];
+  float cn0, cn1;
+  normal_to_sweep(p.rot, rec[1], rec[2], cn0, cn1);
+  const float cn2 = rec[3];
+  const float rd = r[0], rn0 = r[1], rn1 = r[2], rn2 = r[3];
+  h[0] = cd; h[1] = cn0; h[2] = cn1; h[3] = cn2;
+  h[8] = rd; h[9] = rn0; h[10] = rn1; h[11] = rn2;
+  h[12] = cd; h[13] = rn0; h[14] = rn1; h[15] = rn2;
+  h[16] = rd; h[17] = cn0; h[18] = cn1; h[19] = cn2;
+  lds_f32* cf = L.colf + c * 8;
+  cf[0] = p.ref_sum[pix];
+  cf[1] = p.ref_sqsum[pix];
+  cf[2] = cd * (iK[0] * col + iK[1]);
+  cf[3] = cd * (iK[2] * row + iK[3]);
+  cf[4] = cd;
+}
+
+// P2, lane per (column, view): the view's selection prior (:1070-1104); returns the cost-map value for the caller to keep.
+__device__ __forceinline__ float selection_prior(const PmParams& p, const Lds& L, const float* iK, int row, int col0,
+                                                int c, int s, int item) {
+  const int col = col0 + c;
+  const float* rec = p.rec + (size_t)pix_index(p, row, col) * p.rec_stride;
+  const lds_f32* pose = L.poses + s * L.pstride;
+  const lds_f32* h = L.hyp + c * 20;
+  const lds_f32* cf = L.colf + c * 8;
+  const float cost = rec[4 + s];
+  const float beta = rec[p.sel_out_off + s];
+  const float prev = rec[p.sel_in_off + s];
+  L.betav[item] = beta;
+  L.prevv[item] = prev;
+  const float alpha = hmm_message<true>(p, cost, L.fm[item]);
+  const float sp = sel_prob_fn(alpha, beta, prev, p.prev_sel_prob_weight);
+  float cos_tri, cos_inc;
+  viewing_angles(pose, cf[2], cf[3], cf[4], h[1], h[2], h[3], cos_tri, cos_inc);
+  const float tp = tri_prob(p, cos_tri);
+  const float ip = inc_prob(p, cos_inc);
+  float Hm[9];
+  compose_homography(iK, pose, row, col, h[0], h[1], h[2], h[3], Hm);
+  const float rp = res_prob(Hm, (float)row, (float)col, p.radius);
+  L.q[item] = sp * tp * ip * rp;
+  return cost;
+}
+
+// P3a, lane per column: TransformPDFToCDF (:683-696), sequential sum order.
+__device__ __forceinline__ void pdf_to_cdf(const Lds& L, int c, int S) {
+  lds_f32* q = L.q + c * S;
+  float prob_sum = 0.0f;
+#pragma unroll 4
+  for (int i = 0; i < S; ++i) prob_sum += q[i];
+  const float inv_prob_sum = 1.0f / prob_sum;
+  float cum = 0.0f;
+#pragma unroll 4
+  for (int i = 0; i < S; ++i) {
+    cum += q[i] * inv_prob_sum;
+    q[i] = cum;
+  }
+}
+
+// P5b, lane per column: argmin over the five hypotheses (ties go to the later one), the winner stored and kept as the
+// next row's previous state (:1176-1182, 1279-1282).
+__device__ __forceinline__ void pick_best(const PmParams& p, const Lds& L, int row, int col0, int c) {
+  int min_idx = 0;
+  float min_cost = L.csum[c * 5];
+#pragma unroll
+  for (int i = 1; i < 5; ++i) {
+    const float ci = L.csum[c * 5 + i];
+    if (ci <= min_cost) { min_cost = ci; min_idx = i; }
+  }
+  L.best[c] = min_idx;
+  const lds_f32* hb = L.hyp + (c * 5 + min_idx) * 4;
+  const float bd = hb[0], b0 = hb[1], b1 = hb[2], b2 = hb[3];
+  float* rec = p.rec + (size_t)pix_index(p, row, col0 + c) * p.rec_stride;
+  float nx, ny;
+  normal_from_sweep(p.rot, b0, b1, nx, ny);
+  rec[0] = bd; rec[1] = nx; rec[2] = ny; rec[3] = b2;
+  lds_f32* h1 = L.hyp + (c * 5 + 1) * 4;
+  h1[0] = bd; h1[1] = b0; h1[2] = b1; h1[3] = b2;
+}
+
+// P7, lane per (column, view): `cost` = the winner's (hypothesis k) cost against the view; cost map (a winner other
+// than the current plane replaces the stored value), forward message, selection probability (:1186-1207), and with a
+// filter the view's consistency flag (:1209-1265).
+template <bool FILTER_PHOTO, bool FILTER_GEOM>
+__device__ __forceinline__ void forward_and_filter(const PmParams& p, const Lds& L, const float* iK, int row, int col0,
+                                                   int c, int s, int item, int k, float cost) {
+  const int col = col0 + c;
+  float* rec = p.rec + (size_t)pix_index(p, row, col) * p.rec_stride;
+  if (k != 0) rec[4 + s] = cost;
+  const float alpha = hmm_message<true>(p, cost, L.fm[item]);
+  const float prob = sel_prob_fn(alpha, L.betav[item], L.prevv[item], p.prev_sel_prob_weight);
+  L.fm[item] = alpha;
+  rec[p.sel_out_off + s] = prob;
+  if (FILTER_PHOTO || FILTER_GEOM) {
+    const lds_f32* hb = L.hyp + (c * 5 + 1) * 4;  // == best (stored in P5b)
+    const lds_f32* pose = L.poses + s * L.pstride;
+    const float bp0 = hb[0] * (iK[0] * col + iK[1]);
+    const float bp1 = hb[0] * (iK[2] * row + iK[3]);
+    const float bp2 = hb[0];
+    float cos_tri, cos_inc;
+    viewing_angles(pose, bp0, bp1, bp2, hb[1], hb[2], hb[3], cos_tri, cos_inc);
+    int ok = 0;
+    if (!(cos_tri > p.filter_cos_min_tri || cos_inc <= 0.0f)) {
+      const float min_ncc_prob = ncc_prob(p, 1.0f - p.filter_min_ncc);
+      bool photo_ok = true, geom_ok = true;
+      if (FILTER_PHOTO) photo_ok = prob >= min_ncc_prob;
+      if (FILTER_GEOM)
+        geom_ok = geom_cost(p, pose, s, (float)row, (float)col, hb[0]) <= p.filter_geom_max_cost;
+      ok = (photo_ok && geom_ok) ? 1 : 0;
+    }
+    L.flags[item] = ok;
+  }
+}
+
+// P8, lane per column: consistency count (:1267-1275).
+__device__ __forceinline__ void consistency_count(const PmParams& p, const Lds& L, int row, int col0, int c, int S) {
+  int num = 0;
+  for (int s = 0; s < S; ++s) num += L.flags[c * S + s];
+  const int pix = pix_index(p, row, col0 + c);
+  if (num < p.filter_min_num_consistent) {
+    store_filtered_zero(p, p.rec + (size_t)pix * p.rec_stride);
+  } else {
+    for (int s = 0; s < S; ++s)
+      if (L.flags[c * S + s]) p.mask[(size_t)s * p.W * p.H + pix] = 1;
+  }
+}
+
 template <bool GEOM, bool FILTER_PHOTO, bool FILTER_GEOM>
 __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __restrict__ pp) {
   // Batch of reference images: one launch, grid.y problems. Workgroups are dealt to the 8 XCDs
@@ -1234,31 +1415,19 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
 
   lds_load_poses(p, L, GEOM, tid, nt);
 
-  // ---- backward messages for all rows (:976-989); stored in sel_out ----------
+  // ---- backward messages for all rows ----
   for (int item = tid; item < ncols * S; item += nt) {
     const int c = item / S;
-    const int s = item - c * S;
-    float beta = 0.5f;
-    for (int row = RH - 1; row >= 0; --row) {
-      float* rec = p.rec + (size_t)pix_index(p, row, col0 + c) * p.rec_stride;
-      beta = hmm_message<false>(p, rec[4 + s], beta);
-      rec[p.sel_out_off + s] = beta;
-    }
-    L.fm[c * S + s] = 0.5f;
+    backward_messages(p, L, col0, c, item - c * S, S, RH - 1);
   }
 
-  // ---- per-column state kept by the column's lane (:1022-1028) ---------------
+  // ---- per-column state kept by the column's lane: its random stream, the previous row's plane ----
   Rng rng;
   rng.x0 = rng.x1 = rng.x2 = rng.x3 = rng.x4 = rng.d = 0;
   const bool col_lane = tid < ncols;
   if (col_lane) {
-    const int pix0 = pix_index(p, 0, col0 + tid);
-    rng = rng_load(p.rng + (size_t)pix0 * kRngWords);
-    const float* rec = p.rec + (size_t)pix0 * p.rec_stride;
-    float sx, sy;
-    normal_to_sweep(p.rot, rec[1], rec[2], sx, sy);
-    lds_f32* h1 = L.hyp + (tid * 5 + 1) * 4;
-    h1[0] = rec[0]; h1[1] = sx; h1[2] = sy; h1[3] = rec[3];
+    rng = rng_load(p.rng + (size_t)pix_index(p, 0, col0 + tid) * kRngWords);
+    column_init(p, L, col0, tid);
   }
   // reference tile rows [-r, r-1]; row r arrives in the first loop iteration
   for (int r = -p.radius; r < p.radius; ++r) tile_load_row(p, L, col0, r, tid, nt);
@@ -1273,85 +1442,26 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
 
     // ---- P1: hypotheses (lane per column) + patch weights (all lanes) --------
     if (col_lane) {
-      const int c = tid;
-      const int col = col0 + c;
-      const int pix = pix_index(p, row, col);
-      const float* rec = p.rec + (size_t)pix * p.rec_stride;
-      lds_f32* h = L.hyp + c * 20;
-      // propagate the previous row's plane (:1047-1048)
-      h[4] = propagate_depth(iK, h[4], h[6], h[7], (float)(row - 1), (float)row);
-      // current parameters (:1051-1052)
-      const float cd = rec[0];
-      float cn0, cn1;
-      normal_to_sweep(p.rot, rec[1], rec[2], cn0, cn1);
-      const float cn2 = rec[3];
-      // random parameters (:1055-1062)
-      const float dmin = (1.0f - p.perturbation) * cd;
-      const float dmax = (1.0f + p.perturbation) * cd;
-      const float rd = rng_uniform(rng) * (dmax - dmin) + dmin;
-      float rn0, rn1, rn2;
-      perturb_normal(iK, row, col, p.perturbation_pi, cn0, cn1, cn2, rng, rn0, rn1, rn2);
-      for (int m = 0; m < M; ++m) L.us[c * M + m] = rng_uniform(rng) - FLT_EPSILON;  // :1129
-      h[0] = cd; h[1] = cn0; h[2] = cn1; h[3] = cn2;
-      h[8] = rd; h[9] = rn0; h[10] = rn1; h[11] = rn2;
-      h[12] = cd; h[13] = rn0; h[14] = rn1; h[15] = rn2;
-      h[16] = rd; h[17] = cn0; h[18] = cn1; h[19] = cn2;
-      lds_f32* cf = L.colf + c * 8;
-      cf[0] = p.ref_sum[pix];
-      cf[1] = p.ref_sqsum[pix];
-      // ComputePointAtDepth (:1067-1068)
-      cf[2] = cd * (iK[0] * col + iK[1]);
-      cf[3] = cd * (iK[2] * row + iK[3]);
-      cf[4] = cd;
+      const int col = col0 + tid;
+      const float* rec = p.rec + (size_t)pix_index(p, row, col) * p.rec_stride;
+      float r[4];
+      draw_row(p, iK, row, col, M, rec[0], rec[1], rec[2], rec[3], rng, r, L.us + tid * M);
+      row_hypotheses(p, L, iK, row, col0, tid, r);
     }
     patch_weights(p, L, row, tid, nt);
     for (int item = tid; item < ncols * 5 * S; item += nt) L.ncc[item] = -1.0f;
     __syncthreads();
 
-    // ---- P2: per-view selection priors (:1070-1104), lane per (column, view) --
+    // ---- P2: per-view selection priors, lane per (column, view) ----
     patch_weight_sums(p, L, ncols, tid, nt);
     for (int item = tid; item < ncols * S; item += nt) {
       const int c = item / S;
-      const int s = item - c * S;
-      const int col = col0 + c;
-      const float* rec = p.rec + (size_t)pix_index(p, row, col) * p.rec_stride;
-      const lds_f32* pose = L.poses + s * L.pstride;
-      const lds_f32* h = L.hyp + c * 20;
-      const lds_f32* cf = L.colf + c * 8;
-      const float cost = rec[4 + s];
-      const float beta = rec[p.sel_out_off + s];
-      const float prev = rec[p.sel_in_off + s];
-      L.costv[item] = cost;
-      L.betav[item] = beta;
-      L.prevv[item] = prev;
-      const float alpha = hmm_message<true>(p, cost, L.fm[item]);
-      const float sp = sel_prob_fn(alpha, beta, prev, p.prev_sel_prob_weight);
-      float cos_tri, cos_inc;
-      viewing_angles(pose, cf[2], cf[3], cf[4], h[1], h[2], h[3], cos_tri, cos_inc);
-      const float tp = tri_prob(p, cos_tri);
-      const float ip = inc_prob(p, cos_inc);
-      float Hm[9];
-      compose_homography(iK, pose, row, col, h[0], h[1], h[2], h[3], Hm);
-      const float rp = res_prob(Hm, (float)row, (float)col, p.radius);
-      L.q[item] = sp * tp * ip * rp;
+      L.costv[item] = selection_prior(p, L, iK, row, col0, c, item - c * S, item);
     }
     __syncthreads();
 
-    // ---- P3a: TransformPDFToCDF (:683-696), sequential sum order, lane per column
-    if (col_lane) {
-      const int c = tid;
-      lds_f32* q = L.q + c * S;
-      float prob_sum = 0.0f;
-#pragma unroll 4
-      for (int i = 0; i < S; ++i) prob_sum += q[i];
-      const float inv_prob_sum = 1.0f / prob_sum;
-      float cum = 0.0f;
-#pragma unroll 4
-      for (int i = 0; i < S; ++i) {
-        cum += q[i] * inv_prob_sum;
-        q[i] = cum;
-      }
-    }
+    // ---- P3a: PDF to CDF, lane per column ----
+    if (col_lane) pdf_to_cdf(L, tid, S);
     __syncthreads();
     // ---- P3b: Monte-Carlo view draws (:1128-1138), lane per (column, draw) ----
     for (int item = tid; item < ncols * M; item += nt) {
@@ -1400,26 +1510,8 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
       L.csum[item] = acc;
     }
     __syncthreads();
-    // ---- P5b: argmin, store, next row's previous state (:1176-1182,1279-1282) --
-    if (col_lane) {
-      const int c = tid;
-      int min_idx = 0;
-      float min_cost = L.csum[c * 5];
-#pragma unroll
-      for (int i = 1; i < 5; ++i) {
-        const float ci = L.csum[c * 5 + i];
-        if (ci <= min_cost) { min_cost = ci; min_idx = i; }
-      }
-      L.best[c] = min_idx;
-      const lds_f32* hb = L.hyp + (c * 5 + min_idx) * 4;
-      const float bd = hb[0], b0 = hb[1], b1 = hb[2], b2 = hb[3];
-      float* rec = p.rec + (size_t)pix_index(p, row, col0 + c) * p.rec_stride;
-      float nx, ny;
-      normal_from_sweep(p.rot, b0, b1, nx, ny);
-      rec[0] = bd; rec[1] = nx; rec[2] = ny; rec[3] = b2;
-      lds_f32* h1 = L.hyp + (c * 5 + 1) * 4;
-      h1[0] = bd; h1[1] = b0; h1[2] = b1; h1[3] = b2;
-    }
+    // ---- P5b: argmin, store, next row's previous state, lane per column ----
+    if (col_lane) pick_best(p, L, row, col0, tid);
     __syncthreads();
     // ---- P5c: winner vs. the views not evaluated yet, lane per (column, view) --
     for (int item = tid; item < ncols * S; item += nt) {
@@ -1437,60 +1529,18 @@ __global__ void __launch_bounds__(256, 3) pm_sweep_kernel(const PmParams* __rest
     evals2 += (unsigned)run_tasks<false>(p, L, row, col0, tid, nt);
     __syncthreads();
 
-    // ---- P7: cost map, forward message, selection probability (:1186-1207) ---
+    // ---- P7: cost map, forward message, selection probability, filter flags, lane per (column, view) ----
     for (int item = tid; item < ncols * S; item += nt) {
       const int c = item / S;
       const int s = item - c * S;
-      const int col = col0 + c;
       const int k = L.best[c];
-      float* rec = p.rec + (size_t)pix_index(p, row, col) * p.rec_stride;
-      float cost;
-      if (k == 0) {
-        cost = L.costv[item];
-      } else {
-        cost = L.ncc[(c * 5 + k) * S + s];
-        rec[4 + s] = cost;
-      }
-      const float alpha = hmm_message<true>(p, cost, L.fm[item]);
-      const float prob = sel_prob_fn(alpha, L.betav[item], L.prevv[item], p.prev_sel_prob_weight);
-      L.fm[item] = alpha;
-      rec[p.sel_out_off + s] = prob;
-      if (FILTER_PHOTO || FILTER_GEOM) {
-        // :1209-1265
-        const lds_f32* hb = L.hyp + (c * 5 + 1) * 4;  // == best (stored in P5)
-        const lds_f32* pose = L.poses + s * L.pstride;
-        const float bp0 = hb[0] * (iK[0] * col + iK[1]);
-        const float bp1 = hb[0] * (iK[2] * row + iK[3]);
-        const float bp2 = hb[0];
-        float cos_tri, cos_inc;
-        viewing_angles(pose, bp0, bp1, bp2, hb[1], hb[2], hb[3], cos_tri, cos_inc);
-        int ok = 0;
-        if (!(cos_tri > p.filter_cos_min_tri || cos_inc <= 0.0f)) {
-          const float min_ncc_prob = ncc_prob(p, 1.0f - p.filter_min_ncc);
-          bool photo_ok = true, geom_ok = true;
-          if (FILTER_PHOTO) photo_ok = prob >= min_ncc_prob;
-          if (FILTER_GEOM)
-            geom_ok = geom_cost(p, pose, s, (float)row, (float)col, hb[0]) <= p.filter_geom_max_cost;
-          ok = (photo_ok && geom_ok) ? 1 : 0;
-        }
-        L.flags[item] = ok;
-      }
+      const float cost = k == 0 ? L.costv[item] : L.ncc[(c * 5 + k) * S + s];
+      forward_and_filter<FILTER_PHOTO, FILTER_GEOM>(p, L, iK, row, col0, c, s, item, k, cost);
     }
     if (FILTER_PHOTO || FILTER_GEOM) {
       __syncthreads();
-      // ---- P8: consistency count (:1267-1275) ---------------------------------
-      if (col_lane) {
-        const int c = tid;
-        int num = 0;
-        for (int s = 0; s < S; ++s) num += L.flags[c * S + s];
-        const int pix = pix_index(p, row, col0 + c);
-        if (num < p.filter_min_num_consistent) {
-          store_filtered_zero(p, p.rec + (size_t)pix * p.rec_stride);
-        } else {
-          for (int s = 0; s < S; ++s)
-            if (L.flags[c * S + s]) p.mask[(size_t)s * p.W * p.H + pix] = 1;
-        }
-      }
+      // ---- P8: consistency count, lane per column ----
+      if (col_lane) consistency_count(p, L, row, col0, tid, S);
     }
     __syncthreads();
   }
@@ -1964,28 +2014,14 @@ __device__ __forceinline__ void sweep_wave_body(const PmParams* __restrict__ pp)
     return;
   }
 
-  // ---- backward messages for all rows (:976-989); stored in sel_out ----------
+  // ---- backward messages for all rows ----
   for (int item = tid; item < ncols * S; item += nt) {
     const int c = item_div(item, inv_S);
-    const int s = item - c * S;
-    float beta = 0.5f;
-    for (int row = (PM_ABLATE(p) & 4) ? -1 : RH - 1; row >= 0; --row) {
-      float* rec = p.rec + (size_t)pix_index(p, row, col0 + c) * p.rec_stride;
-      beta = hmm_message<false>(p, rec[4 + s], beta);
-      rec[p.sel_out_off + s] = beta;
-    }
-    L.fm[c * S + s] = 0.5f;
+    backward_messages(p, L, col0, c, item - c * S, S, (PM_ABLATE(p) & 4) ? -1 : RH - 1);
   }
 
-  // ---- per-column state kept across rows: the previous row's plane (:1022-1028) ----
-  if (tid < ncols) {
-    const int pix0 = pix_index(p, 0, col0 + tid);
-    const float* rec = p.rec + (size_t)pix0 * p.rec_stride;
-    float sx, sy;
-    normal_to_sweep(p.rot, rec[1], rec[2], sx, sy);
-    lds_f32* h1 = L.hyp + (tid * 5 + 1) * 4;
-    h1[0] = rec[0]; h1[1] = sx; h1[2] = sy; h1[3] = rec[3];
-  }
+  // ---- per-column state kept across rows: the previous row's plane ----
+  if (tid < ncols) column_init(p, L, col0, tid);
   // written once: the zero slots behind the S views of every (column, hypothesis) row and the seven padding taps
   for (int i = tid; i < C * 5; i += nt) {
     L.cost5[i * S1 + S] = 0.0f;
@@ -2022,30 +2058,9 @@ __device__ __forceinline__ void sweep_wave_body(const PmParams* __restrict__ pp)
 
     PM_PROF_MARK(kProfP0)
     PM_MARK("P1");
-    // ---- P1: hypotheses, lane per column (:1047-1068); the random ones come from pm_draw_kernel ----
+    // ---- P1: hypotheses, lane per column; the random ones come from pm_draw_kernel ----
     if (col_lane && !(PM_ABLATE(p) & 2)) {
-      const int c = tid;
-      const int col = col0 + c;
-      const int pix = pix_index(p, row, col);
-      const float* rec = p.rec + (size_t)pix * p.rec_stride;
-      gbl_f32* dr = draws + ((size_t)row * RW + col) * dstride;
-      lds_f32* h = L.hyp + c * 20;
-      h[4] = propagate_depth(iK, h[4], h[6], h[7], (float)(row - 1), (float)row);
-      const float cd = rec[0];
-      float cn0, cn1;
-      normal_to_sweep(p.rot, rec[1], rec[2], cn0, cn1);
-      const float cn2 = rec[3];
-      const float rd = dr[0], rn0 = dr[1], rn1 = dr[2], rn2 = dr[3];
-      h[0] = cd; h[1] = cn0; h[2] = cn1; h[3] = cn2;
-      h[8] = rd; h[9] = rn0; h[10] = rn1; h[11] = rn2;
-      h[12] = cd; h[13] = rn0; h[14] = rn1; h[15] = rn2;
-      h[16] = rd; h[17] = cn0; h[18] = cn1; h[19] = cn2;
-      lds_f32* cf = L.colf + c * 8;
-      cf[0] = p.ref_sum[pix];
-      cf[1] = p.ref_sqsum[pix];
-      cf[2] = cd * (iK[0] * col + iK[1]);
-      cf[3] = cd * (iK[2] * row + iK[3]);
-      cf[4] = cd;
+      row_hypotheses(p, L, iK, row, col0, tid, draws + ((size_t)row * RW + col0 + tid) * dstride);
     }
     PM_PROF_MARK(kProfP1)
     PM_MARK("P1w");
@@ -2055,52 +2070,19 @@ __device__ __forceinline__ void sweep_wave_body(const PmParams* __restrict__ pp)
     PM_PROF_MARK(kProfP1w)
     PM_MARK("P2");
 
-    // ---- P2: per-view selection priors (:1070-1104), lane per (column, view) --
+    // ---- P2: per-view selection priors, lane per (column, view) ----
     patch_weight_sums(p, L, ncols, tid, nt);
     for (int item = tid; item < ncols * S; item += nt) {
       const int c = item_div(item, inv_S);
       const int s = item - c * S;
-      const int col = col0 + c;
-      const float* rec = p.rec + (size_t)pix_index(p, row, col) * p.rec_stride;
-      const lds_f32* pose = L.poses + s * L.pstride;
-      const lds_f32* h = L.hyp + c * 20;
-      const lds_f32* cf = L.colf + c * 8;
-      const float cost = rec[4 + s];
-      const float beta = rec[p.sel_out_off + s];
-      const float prev = rec[p.sel_in_off + s];
-      L.cost5[c * 5 * S1 + s] = cost;
-      L.betav[item] = beta;
-      L.prevv[item] = prev;
-      const float alpha = hmm_message<true>(p, cost, L.fm[item]);
-      const float sp = sel_prob_fn(alpha, beta, prev, p.prev_sel_prob_weight);
-      float cos_tri, cos_inc;
-      viewing_angles(pose, cf[2], cf[3], cf[4], h[1], h[2], h[3], cos_tri, cos_inc);
-      const float tp = tri_prob(p, cos_tri);
-      const float ip = inc_prob(p, cos_inc);
-      float Hm[9];
-      compose_homography(iK, pose, row, col, h[0], h[1], h[2], h[3], Hm);
-      const float rp = res_prob(Hm, (float)row, (float)col, p.radius);
-      L.q[item] = sp * tp * ip * rp;
+      L.cost5[c * 5 * S1 + s] = selection_prior(p, L, iK, row, col0, c, s, item);
     }
     wave_sync<NW>();
 
     PM_PROF_MARK(kProfP2)
     PM_MARK("P3a");
-    // ---- P3a: TransformPDFToCDF (:683-696), sequential sum order, lane per column
-    if (col_lane) {
-      const int c = tid;
-      lds_f32* q = L.q + c * S;
-      float prob_sum = 0.0f;
-#pragma unroll 4
-      for (int i = 0; i < S; ++i) prob_sum += q[i];
-      const float inv_prob_sum = 1.0f / prob_sum;
-      float cum = 0.0f;
-#pragma unroll 4
-      for (int i = 0; i < S; ++i) {
-        cum += q[i] * inv_prob_sum;
-        q[i] = cum;
-      }
-    }
+    // ---- P3a: PDF to CDF, lane per column ----
+    if (col_lane) pdf_to_cdf(L, tid, S);
     wave_sync<NW>();
     PM_PROF_MARK(kProfP3a)
     PM_MARK("P3b");
@@ -2190,26 +2172,8 @@ __device__ __forceinline__ void sweep_wave_body(const PmParams* __restrict__ pp)
     wave_sync<NW>();
     PM_PROF_MARK(kProfP5a)
     PM_MARK("P5b");
-    // ---- P5b: argmin, store, next row's previous state (:1176-1182,1279-1282) --
-    if (col_lane) {
-      const int c = tid;
-      int min_idx = 0;
-      float min_cost = L.csum[c * 5];
-#pragma unroll
-      for (int i = 1; i < 5; ++i) {
-        const float ci = L.csum[c * 5 + i];
-        if (ci <= min_cost) { min_cost = ci; min_idx = i; }
-      }
-      L.best[c] = min_idx;
-      const lds_f32* hb = L.hyp + (c * 5 + min_idx) * 4;
-      const float bd = hb[0], b0 = hb[1], b1 = hb[2], b2 = hb[3];
-      float* rec = p.rec + (size_t)pix_index(p, row, col0 + c) * p.rec_stride;
-      float nx, ny;
-      normal_from_sweep(p.rot, b0, b1, nx, ny);
-      rec[0] = bd; rec[1] = nx; rec[2] = ny; rec[3] = b2;
-      lds_f32* h1 = L.hyp + (c * 5 + 1) * 4;
-      h1[0] = bd; h1[1] = b0; h1[2] = b1; h1[3] = b2;
-    }
+    // ---- P5b: argmin, store, next row's previous state, lane per column ----
+    if (col_lane) pick_best(p, L, row, col0, tid);
     wave_sync<NW>();
     PM_PROF_MARK(kProfP5b)
     PM_MARK("P5c");
@@ -2244,55 +2208,19 @@ __device__ __forceinline__ void sweep_wave_body(const PmParams* __restrict__ pp)
     PM_PROF_MARK(kProfP6F)
     PM_MARK("P7");
 
-    // ---- P7: cost map, forward message, selection probability (:1186-1207) ---
+    // ---- P7: cost map, forward message, selection probability, filter flags, lane per (column, view) ----
     for (int item = tid; item < ncols * S; item += nt) {
       const int c = item_div(item, inv_S);
       const int s = item - c * S;
-      const int col = col0 + c;
       const int k = L.best[c];
-      float* rec = p.rec + (size_t)pix_index(p, row, col) * p.rec_stride;
-      const float cost = L.cost5[(c * 5 + k) * S1 + s];
-      if (k != 0) rec[4 + s] = cost;
-      const float alpha = hmm_message<true>(p, cost, L.fm[item]);
-      const float prob = sel_prob_fn(alpha, L.betav[item], L.prevv[item], p.prev_sel_prob_weight);
-      L.fm[item] = alpha;
-      rec[p.sel_out_off + s] = prob;
-      if (FILTER_PHOTO || FILTER_GEOM) {
-        const lds_f32* hb = L.hyp + (c * 5 + 1) * 4;  // == best (stored in P5)
-        const lds_f32* pose = L.poses + s * L.pstride;
-        const float bp0 = hb[0] * (iK[0] * col + iK[1]);
-        const float bp1 = hb[0] * (iK[2] * row + iK[3]);
-        const float bp2 = hb[0];
-        float cos_tri, cos_inc;
-        viewing_angles(pose, bp0, bp1, bp2, hb[1], hb[2], hb[3], cos_tri, cos_inc);
-        int ok = 0;
-        if (!(cos_tri > p.filter_cos_min_tri || cos_inc <= 0.0f)) {
-          const float min_ncc_prob = ncc_prob(p, 1.0f - p.filter_min_ncc);
-          bool photo_ok = true, geom_ok = true;
-          if (FILTER_PHOTO) photo_ok = prob >= min_ncc_prob;
-          if (FILTER_GEOM)
-            geom_ok = geom_cost(p, pose, s, (float)row, (float)col, hb[0]) <= p.filter_geom_max_cost;
-          ok = (photo_ok && geom_ok) ? 1 : 0;
-        }
-        L.flags[item] = ok;
-      }
+      forward_and_filter<FILTER_PHOTO, FILTER_GEOM>(p, L, iK, row, col0, c, s, item, k, L.cost5[(c * 5 + k) * S1 + s]);
     }
     PM_PROF_MARK(kProfP7)
     if (FILTER_PHOTO || FILTER_GEOM) {
       wave_sync<NW>();
       PM_MARK("P8");
-      if (col_lane) {
-        const int c = tid;
-        int num = 0;
-        for (int s = 0; s < S; ++s) num += L.flags[c * S + s];
-        const int pix = pix_index(p, row, col0 + c);
-        if (num < p.filter_min_num_consistent) {
-          store_filtered_zero(p, p.rec + (size_t)pix * p.rec_stride);
-        } else {
-          for (int s = 0; s < S; ++s)
-            if (L.flags[c * S + s]) p.mask[(size_t)s * p.W * p.H + pix] = 1;
-        }
-      }
+      // ---- P8: consistency count, lane per column ----
+      if (col_lane) consistency_count(p, L, row, col0, tid, S);
     }
     wave_sync<NW>();
     PM_MARK("ROWEND");
@@ -2461,16 +2389,8 @@ __global__ void __launch_bounds__(64) pm_draw_kernel(const PmParams* __restrict_
       const float* nrec = p.rec + (size_t)pix_index(p, row + 1, col) * p.rec_stride;
       nd = nrec[0]; n1 = nrec[1]; n2 = nrec[2]; n3 = nrec[3];
     }
-    float cn0, cn1;
-    normal_to_sweep(p.rot, r1, r2, cn0, cn1);
-    const float dmin = (1.0f - p.perturbation) * cd;
-    const float dmax = (1.0f + p.perturbation) * cd;
-    const float rd = rng_uniform(rng) * (dmax - dmin) + dmin;
-    float rn0, rn1, rn2;
-    perturb_normal(iK, row, col, p.perturbation_pi, cn0, cn1, cn2, rng, rn0, rn1, rn2);
     float* o = out + (size_t)row * RW * dstride;
-    o[0] = rd; o[1] = rn0; o[2] = rn1; o[3] = rn2;
-    for (int m = 0; m < M; ++m) o[4 + m] = rng_uniform(rng) - FLT_EPSILON;  // :1129
+    draw_row(p, iK, row, col, M, cd, r1, r2, cn2, rng, o, o + 4);
     cd = nd; r1 = n1; r2 = n2; cn2 = n3;
   }
   rng_store(rng_at, rng);  // :1285-1287
