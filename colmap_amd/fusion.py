@@ -19,6 +19,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import model_statistics
 from . import mvs
 from . import workspace as W
 from ._lib import lib
@@ -319,7 +320,8 @@ class StereoFusion:
         with open(cfg) as f:
             names = [l.strip() for l in f if l.strip() and not l.startswith("#")]
         overlapping = model.GetMaxOverlappingImagesFromPMVS() or \
-            model.GetMaxOverlappingImages(self.options_.check_num_images, 0.0)  # (:180-186)
+            model_statistics.get_max_overlapping_images(model, self.options_.check_num_images, 0.0)  # (:180-186), on
+        # the device the fusion itself runs on
         images = [FusionImage(im.width, im.height, im.K, im.R, im.T, None, None, None, used=False) for im in model.images]
         for name in names:
             idx = model.GetImageIdx(name)

@@ -529,10 +529,13 @@ class PatchMatchController:
 
     @classmethod
     def FromWorkspace(cls, options: PatchMatchOptions, workspace_path: str, workspace_format: str = "COLMAP",
-                      pmvs_option_name: str = "option-all", config_path: str = "", **kw) -> "PatchMatchController":
+                      pmvs_option_name: str = "option-all", config_path: str = "", model_statistics=None,
+                      **kw) -> "PatchMatchController":
         """PatchMatchController(options, workspace_path, workspace_format, pmvs_option_name,
         config_path) + ReadWorkspace + ReadProblems (patch_match.cc:159-237,239-359): the undistorted
-        COLMAP workspace on disk -- `sparse/` model, `images/`, `stereo/patch-match.cfg`."""
+        COLMAP workspace on disk -- `sparse/` model, `images/`, `stereo/patch-match.cfg`.
+        model_statistics: None takes the `__auto__` lists and the depth ranges from the methods of
+        the workspace's model, in Python; a model_statistics.DeviceStatistics computes them on the GPU."""
         import os
         from . import workspace as W
         pmvs = workspace_format.lower() == "pmvs"
@@ -546,8 +549,9 @@ class PatchMatchController:
         with open(cfg) as f:
             lines = f.read().splitlines()
         warnings: List[str] = []
-        problems = W.read_patch_match_config(lines, model, options.min_triangulation_angle, warnings.append)
-        ranges = model.ComputeDepthRanges()
+        problems = W.read_patch_match_config(lines, model, options.min_triangulation_angle, warnings.append,
+                                             model_statistics=model_statistics)
+        ranges = model.ComputeDepthRanges() if model_statistics is None else model_statistics.compute_depth_ranges(model)
         used = sorted({i for ref, src in problems for i in [ref] + src})
         images = []
         for idx, im in enumerate(model.images):

@@ -16,6 +16,7 @@ import dataclasses
 import os
 import sys
 
+from . import model_statistics
 from . import mvs
 
 
@@ -68,6 +69,7 @@ def main(argv=None) -> int:
     elif opt.gpu_index == "-1":
         opt.gpu_index = "0"  # ReadGpuIndices (:361-375): all devices; one process drives one GPU here
     ctl = mvs.PatchMatchController.FromWorkspace(opt, a.workspace_path, fmt, a.pmvs_option_name, a.config_path,
+                                                 model_statistics=model_statistics.DeviceStatistics(int(str(opt.gpu_index).split(",")[0])),
                                                  batch_size=a.batch_size, rank=rank, world_size=world)
     for w in getattr(ctl, "warnings_", []):
         print("W", w, file=sys.stderr)

@@ -9,12 +9,13 @@ patch_match_stereo, stereo_fusion, bundle_adjustment, filter_points, undistort_i
 def patch_match_stereo(workspace_path, workspace_format="COLMAP", pmvs_option_name="option-all", options=None,
                        config_path=""):
     """pycolmap.patch_match_stereo: runs PatchMatch stereo on an undistorted workspace (needs an MI355X)."""
-    from . import mvs
+    from . import model_statistics, mvs
     opt = options or mvs.PatchMatchOptions()
     if opt.gpu_index == "-1":
         opt.gpu_index = "0"
     ctl = mvs.PatchMatchController.FromWorkspace(opt, str(workspace_path), workspace_format.lower(), pmvs_option_name,
-                                                 str(config_path))
+                                                 str(config_path),
+                                                 model_statistics=model_statistics.DeviceStatistics(int(str(opt.gpu_index).split(",")[0])))
     ctl.Run()
     return ctl
 

@@ -714,11 +714,13 @@ class Model:
 # ------------------------------------------------------------------------------------------------
 
 def read_patch_match_config(lines: Sequence[str], model: Model, min_triangulation_angle: float = 1.0,
-                            warn=None) -> List[Tuple[int, List[int]]]:
+                            warn=None, model_statistics=None) -> List[Tuple[int, List[int]]]:
     """PatchMatchController::ReadProblems: pairs of lines (reference image name, source spec);
     the spec is `__all__`, `__auto__, N` (N most-overlapping images whose 75th-percentile
     triangulation angle reaches PatchMatchOptions::min_triangulation_angle) or a comma-separated
-    list of image names. Reference images without sources are dropped with a warning."""
+    list of image names. Reference images without sources are dropped with a warning.
+    model_statistics: None computes the `__auto__` lists with the methods of `model`, here; a
+    model_statistics.DeviceStatistics takes them from the GPU (one call per distinct N)."""
     configs = []
     ref_name = ""
     for raw in lines:
@@ -731,12 +733,18 @@ def read_patch_match_config(lines: Sequence[str], model: Model, min_triangulatio
         configs.append((ref_name, [t.strip() for t in line.split(",") if t.strip()]))
         ref_name = ""
     shared = angles = None
+    device_lists: Dict[int, List[List[int]]] = {}
     min_rad = np.float32(np.deg2rad(min_triangulation_angle))
     problems = []
     for ref_name, srcs in configs:
         ref = model.GetImageIdx(ref_name)
         if len(srcs) == 1 and srcs[0] == "__all__":
             src = [i for i in range(len(model.images)) if i != ref]
+        elif len(srcs) == 2 and srcs[0] == "__auto__" and model_statistics is not None:
+            max_num = int(srcs[1])
+            if max_num not in device_lists:
+                device_lists[max_num] = model_statistics.get_max_overlapping_images(model, max_num, min_triangulation_angle)
+            src = device_lists[max_num][ref]
         elif len(srcs) == 2 and srcs[0] == "__auto__":
             if shared is None:
                 shared = model.ComputeSharedPoints()
