@@ -13,6 +13,7 @@ from __future__ import annotations
 import argparse
 import os
 import sys
+from dataclasses import replace
 from typing import Optional
 
 import numpy as np
@@ -54,7 +55,7 @@ def reconstruction_from_sparse_model(sm: W.SparseModel) -> scene.Reconstruction:
     reconstruction_io_binary.cc:176-214); rigs with a single sensor stay trivial frames too."""
     rec = scene.Reconstruction()
     for cid, c in sm.cameras.items():
-        rec.cameras[cid] = scene.Camera(cid, c.model_id, c.width, c.height, np.array(c.params, np.float64))
+        rec.cameras[cid] = replace(c, camera_id=cid, params=np.array(c.params, np.float64))
     frame_of_image = {}
     for rid, rig in sm.rigs.items():
         cam_sensors = {sid: pose for sid, pose in rig.sensors.items() if sid[0] == _CAMERA}
@@ -103,7 +104,7 @@ def sparse_model_from_reconstruction(rec: scene.Reconstruction, names: Optional[
     """The inverse of reconstruction_from_sparse_model (used to put synthetic datasets on disk)."""
     sm = W.SparseModel()
     for cid, c in rec.cameras.items():
-        sm.cameras[cid] = W.SparseCamera(cid, c.model_id, c.width, c.height, np.array(c.params, np.float64))
+        sm.cameras[cid] = replace(c, camera_id=cid, params=np.array(c.params, np.float64))
     for iid, img in rec.images.items():
         p = _wxyz_t(img.cam_from_world)
         xys = np.array([q.xy for q in img.points2D], np.float64).reshape(-1, 2)

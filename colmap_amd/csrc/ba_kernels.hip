@@ -58,8 +58,6 @@ using ba_layout::NPAR;
 using ba_layout::TIER_MAX;
 using ba_layout::TIER_NARROW;
 using ba_layout::TIER_WIDE;
-using ba_layout::model_supported;
-using ba_layout::num_params_of;
 
 extern "C" void pm_release_cached_memory(void);  // pm_api.cpp (same library)
 
@@ -4366,7 +4364,8 @@ static int64_t ShardNumObservations(const ba_problem* p, int32_t rank, int32_t w
   if (!p || world_size < 1 || rank < 0 || rank >= world_size) return -1;
   std::vector<int> cam_nvar(p->num_cams, 0);
   for (int k = 0; k < p->num_cams; ++k) {
-    const int P = num_params_of(p->cam_model[k]);
+    const int P = colmap_amd::camera_models::num_params(p->cam_model[k]);
+    if (P < 0) return -1;
     for (int j = 0; j < P; ++j)
       if (!p->cam_const[(size_t)k * BA_CAM_STRIDE + j]) ++cam_nvar[k];
   }

@@ -6,6 +6,7 @@
 #ifndef COLMAP_AMD_BA_LAYOUT_H_
 #define COLMAP_AMD_BA_LAYOUT_H_
 
+#include "../../include/colmap_amd/camera_models.hpp"
 #include "../../include/colmap_amd_ba.h"
 
 #include <algorithm>
@@ -20,35 +21,20 @@
 #include <utility>
 #include <vector>
 
-// The camera-model table is read by the kernels too: host/device qualifiers when the HIP header (or its stand-in)
-// came first, plain inline otherwise.
-#if defined(__device__) && defined(__host__)
-#define BA_LAYOUT_HD __device__ __host__ __forceinline__
-#else
-#define BA_LAYOUT_HD inline
-#endif
-
 namespace ba_layout {
 
-BA_LAYOUT_HD int num_params_of(int model) {
-  switch (model) {
-    case BA_SIMPLE_PINHOLE: case BA_SIMPLE_FISHEYE: return 3;
-    case BA_RADIAL: case BA_RADIAL_FISHEYE: case BA_FOV: case BA_DIVISION: return 5;
-    case BA_EUCM: return 6;
-    case BA_OPENCV: case BA_OPENCV_FISHEYE: return 8;
-    case BA_FULL_OPENCV: case BA_THIN_PRISM_FISHEYE: return 12;
-    case BA_RAD_TAN_THIN_PRISM_FISHEYE: return 16;
-    case BA_EQUIRECTANGULAR: return 2;
-    default: return 4;  // PINHOLE, SIMPLE_RADIAL, SIMPLE_RADIAL_FISHEYE, SIMPLE_DIVISION, FISHEYE
-  }
-}
-inline bool model_supported(int model) {
-  return model == BA_SIMPLE_PINHOLE || model == BA_PINHOLE || model == BA_SIMPLE_RADIAL || model == BA_RADIAL ||
-         model == BA_OPENCV || model == BA_OPENCV_FISHEYE || model == BA_SIMPLE_RADIAL_FISHEYE ||
-         model == BA_RADIAL_FISHEYE || model == BA_FOV || model == BA_SIMPLE_DIVISION || model == BA_DIVISION ||
-         model == BA_SIMPLE_FISHEYE || model == BA_FISHEYE || model == BA_EUCM || model == BA_FULL_OPENCV ||
-         model == BA_THIN_PRISM_FISHEYE || model == BA_RAD_TAN_THIN_PRISM_FISHEYE || model == BA_EQUIRECTANGULAR;
-}
+namespace models = colmap_amd::camera_models;
+
+// The BA_* ids are ABI (colmap_amd_ba.h); the table is where everything else about a model is read.
+#define BA_SAME_ID(name) static_assert(int(BA_##name) == int(models::name), "colmap_amd_ba.h and camera_models.hpp disagree on " #name)
+BA_SAME_ID(SIMPLE_PINHOLE); BA_SAME_ID(PINHOLE); BA_SAME_ID(SIMPLE_RADIAL); BA_SAME_ID(RADIAL); BA_SAME_ID(OPENCV);
+BA_SAME_ID(OPENCV_FISHEYE); BA_SAME_ID(FULL_OPENCV); BA_SAME_ID(FOV); BA_SAME_ID(SIMPLE_RADIAL_FISHEYE);
+BA_SAME_ID(RADIAL_FISHEYE); BA_SAME_ID(THIN_PRISM_FISHEYE); BA_SAME_ID(RAD_TAN_THIN_PRISM_FISHEYE);
+BA_SAME_ID(SIMPLE_DIVISION); BA_SAME_ID(DIVISION); BA_SAME_ID(SIMPLE_FISHEYE); BA_SAME_ID(FISHEYE); BA_SAME_ID(EUCM);
+BA_SAME_ID(EQUIRECTANGULAR);
+#undef BA_SAME_ID
+static_assert(models::kNumModels == 18, "a model without a BA_* id");
+static_assert(BA_CAM_STRIDE == models::kMaxParams, "BA_CAM_STRIDE holds the largest model");
 
 // Host-side set-up loops over the observations (gathers into the device orders: random reads that one core serves at
 // a cache miss a time): contiguous index ranges on up to 16 threads. fn(begin, end, thread).
@@ -170,13 +156,13 @@ inline void count_variable_intrinsics(const ba_problem& p, Layout& L) {
   L.cam_var.assign((size_t)p.num_cams * BA_CAM_STRIDE, 0);
   for (int k = 0; k < p.num_cams; ++k) {
     const int model = p.cam_model[k];
-    if (!model_supported(model))
+    const int P = models::num_params(model);
+    if (P < 0)
       throw std::runtime_error("unsupported camera model id " + std::to_string(model) +
                                " (supported: SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, "
                                "OPENCV_FISHEYE, FOV, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE, SIMPLE_DIVISION, "
                                "DIVISION, SIMPLE_FISHEYE, FISHEYE, EUCM, FULL_OPENCV, THIN_PRISM_FISHEYE, "
                                "RAD_TAN_THIN_PRISM_FISHEYE, EQUIRECTANGULAR)");
-    const int P = num_params_of(model);
     for (int j = 0; j < P; ++j)
       if (!p.cam_const[(size_t)k * BA_CAM_STRIDE + j]) L.cam_var[(size_t)k * BA_CAM_STRIDE + L.cam_nvar[k]++] = j;
     L.max_nvar = std::max(L.max_nvar, L.cam_nvar[k]);

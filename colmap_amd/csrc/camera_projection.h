@@ -1,4 +1,6 @@
-// undistort_models.h -- the camera models of image undistortion, once, for host and device.
+// camera_projection.h -- the projections of the camera models, once, for host and device: image undistortion
+// (undistort.hip) and observation filtering (obs_filter.hip) both read it. What a model IS (id, parameters, family)
+// comes from include/colmap_amd/camera_models.hpp.
 //
 // Restates, for the 17 perspective models and EQUIRECTANGULAR (reference src/colmap/sensor/models.h):
 //   Distortion(extra, u, v) -> (du, dv)       the additive distortion of each model, in the reference's order of
@@ -15,72 +17,24 @@
 //
 // Everything is double; the build has -ffp-contract=off, so an expression rounds the same on the host and on gfx950.
 // What may differ between the two is libm (atan, tan, sin, cos): see DESIGN.md section 1.9 for the parity rule.
-//
-// ---- the resize filter (undistort_resize_kernel, the indirect path of WarpImageBetweenCameras) ----
-// The reference shrinks with OpenImageIO's default filter, which is not restated here. This library shrinks with an
-// antialiased separable triangle filter: per axis with s = source size / target size and support r = max(s, 1), target
-// pixel i has its centre at c = (i + 0.5) * s in source coordinates and takes source pixel j (centre j + 0.5) with weight
-// w(j) = max(0, 1 - |j + 0.5 - c| / r) for j = floor(c - r) .. ceil(c + r), restricted to 0 <= j < source size. The value
-// is sum_y wy * (sum_x wx * p(x, y)) divided by (sum_x wx) * (sum_y wy) over the taken pixels (so that a border pixel is
-// a weighted mean of what exists), summed in that order in double, then cast to float, rounded and clamped to [0, 255]
-// like every other pixel (sensor/bitmap.h:216-223). At s = 1 it is the identity; for s <= 1 it is bilinear interpolation.
-#ifndef COLMAP_AMD_UNDISTORT_MODELS_H_
-#define COLMAP_AMD_UNDISTORT_MODELS_H_
+#ifndef COLMAP_AMD_CAMERA_PROJECTION_H_
+#define COLMAP_AMD_CAMERA_PROJECTION_H_
 
 #include <math.h>
 
-#define UD_HD __host__ __device__ __forceinline__
+#include "../../include/colmap_amd/camera_models.hpp"  // after the HIP header: its functions are host/device here
 
-namespace undistort {
+#define CAM_HD __host__ __device__ __forceinline__
 
-// colmap::CameraModelId (sensor/models.h:90-111)
-enum Model : int {
-  SIMPLE_PINHOLE = 0, PINHOLE = 1, SIMPLE_RADIAL = 2, RADIAL = 3, OPENCV = 4, OPENCV_FISHEYE = 5, FULL_OPENCV = 6,
-  FOV = 7, SIMPLE_RADIAL_FISHEYE = 8, RADIAL_FISHEYE = 9, THIN_PRISM_FISHEYE = 10, RAD_TAN_THIN_PRISM_FISHEYE = 11,
-  SIMPLE_DIVISION = 12, DIVISION = 13, SIMPLE_FISHEYE = 14, FISHEYE = 15, EUCM = 16, EQUIRECTANGULAR = 17,
-  NUM_MODELS = 18
-};
-constexpr int kMaxParams = 16;
+namespace camera {
+
+using namespace colmap_amd::camera_models;  // the ids, kMaxParams, num_params, the predicates, intrinsics
+
 constexpr double kEps = 2.220446049250313e-16;  // std::numeric_limits<double>::epsilon()
 constexpr double kPi = 3.141592653589793238462643383279502884;
 
-UD_HD int num_params(int m) {
-  switch (m) {
-    case SIMPLE_PINHOLE: case SIMPLE_FISHEYE: return 3;
-    case PINHOLE: case SIMPLE_RADIAL: case SIMPLE_RADIAL_FISHEYE: case SIMPLE_DIVISION: case FISHEYE: return 4;
-    case RADIAL: case FOV: case RADIAL_FISHEYE: case DIVISION: return 5;
-    case EUCM: return 6;
-    case OPENCV: case OPENCV_FISHEYE: return 8;
-    case FULL_OPENCV: case THIN_PRISM_FISHEYE: return 12;
-    case RAD_TAN_THIN_PRISM_FISHEYE: return 16;
-    case EQUIRECTANGULAR: return 2;
-  }
-  return -1;
-}
-// one shared focal length (f, cx, cy, extra...) or two (fx, fy, cx, cy, extra...)
-UD_HD bool one_focal(int m) {
-  return m == SIMPLE_PINHOLE || m == SIMPLE_RADIAL || m == RADIAL || m == SIMPLE_RADIAL_FISHEYE || m == RADIAL_FISHEYE ||
-         m == SIMPLE_DIVISION || m == SIMPLE_FISHEYE;
-}
-UD_HD bool is_spherical(int m) { return m == EQUIRECTANGULAR; }
-UD_HD bool is_perspective(int m) { return m >= 0 && m < EQUIRECTANGULAR; }
-// BasePerspectiveFisheyeCameraModel (models.h:425-456)
-UD_HD bool is_fisheye(int m) {
-  return m == OPENCV_FISHEYE || m == SIMPLE_RADIAL_FISHEYE || m == RADIAL_FISHEYE || m == THIN_PRISM_FISHEYE ||
-         m == RAD_TAN_THIN_PRISM_FISHEYE || m == SIMPLE_FISHEYE || m == FISHEYE;
-}
-
-struct Intrinsics {
-  double f1, f2, c1, c2;
-  const double* extra;
-};
-UD_HD Intrinsics intrinsics(int m, const double* p) {
-  if (one_focal(m)) return Intrinsics{p[0], p[0], p[1], p[2], p + 3};
-  return Intrinsics{p[0], p[1], p[2], p[3], p + 4};
-}
-
 // FisheyeFromNormal / NormalFromFisheye (models.h:429-451)
-UD_HD void fisheye_from_normal(double u, double v, double* uu, double* vv) {
+CAM_HD void fisheye_from_normal(double u, double v, double* uu, double* vv) {
   *uu = u;
   *vv = v;
   const double r = sqrt(u * u + v * v);
@@ -90,7 +44,7 @@ UD_HD void fisheye_from_normal(double u, double v, double* uu, double* vv) {
     *vv *= theta / r;
   }
 }
-UD_HD void normal_from_fisheye(double uu, double vv, double* u, double* v) {
+CAM_HD void normal_from_fisheye(double uu, double vv, double* u, double* v) {
   *u = uu;
   *v = vv;
   const double theta = sqrt(uu * uu + vv * vv);
@@ -105,8 +59,8 @@ UD_HD void normal_from_fisheye(double uu, double vv, double* u, double* v) {
 // radial polynomial + tangential + thin-prism family:
 //   du = u * rad + 2 t1 u v + t2 (r2 + 2 u^2) + sx r2,   dv = v * rad + 2 t2 u v + t1 (r2 + 2 v^2) + sy r2
 // with rad = rad(r2), drad = d rad / d r2. J = d(du, dv) / d(u, v), row-major.
-UD_HD void family_jacobian(double u, double v, double rad, double drad, double t1, double t2, double sx, double sy,
-                           double* J) {
+CAM_HD void family_jacobian(double u, double v, double rad, double drad, double t1, double t2, double sx, double sy,
+                            double* J) {
   J[0] = rad + 2.0 * u * u * drad + 2.0 * t1 * v + 6.0 * t2 * u + 2.0 * sx * u;
   J[1] = 2.0 * u * v * drad + 2.0 * t1 * u + 2.0 * t2 * v + 2.0 * sx * v;
   J[2] = 2.0 * u * v * drad + 2.0 * t2 * v + 2.0 * t1 * u + 2.0 * sy * u;
@@ -115,7 +69,7 @@ UD_HD void family_jacobian(double u, double v, double rad, double drad, double t
 
 // CameraModel::Distortion of the models that have an additive one; e = extra parameters. J may be null. For the
 // fisheye models (u, v) are the equidistant coordinates. Operation order of the values as in the reference.
-UD_HD void distortion(int m, const double* e, double u, double v, double* du, double* dv, double* J) {
+CAM_HD void distortion(int m, const double* e, double u, double v, double* du, double* dv, double* J) {
   const double u2 = u * u, uv = u * v, v2 = v * v, r2 = u2 + v2;
   switch (m) {
     case SIMPLE_RADIAL: case SIMPLE_RADIAL_FISHEYE: {  // models.h:1392-1403, 2013-2022
@@ -217,7 +171,7 @@ UD_HD void distortion(int m, const double* e, double u, double v, double* du, do
 }
 
 // FOVCameraModel::Distortion / Undistortion (models.h:1852-1926): multiplicative, (u, v) -> (u, v) * factor
-UD_HD double fov_distortion_factor(double omega, double radius2) {
+CAM_HD double fov_distortion_factor(double omega, double radius2) {
   const double kEpsilon = 1e-4;
   const double omega2 = omega * omega;
   if (omega2 < kEpsilon) return (omega2 * radius2) / 3.0 - omega2 / 12.0 + 1.0;
@@ -228,7 +182,7 @@ UD_HD double fov_distortion_factor(double omega, double radius2) {
   const double radius = sqrt(radius2);
   return atan(radius * 2.0 * tan(omega / 2.0)) / (radius * omega);
 }
-UD_HD double fov_undistortion_factor(double omega, double radius2) {
+CAM_HD double fov_undistortion_factor(double omega, double radius2) {
   const double kEpsilon = 1e-4;
   const double omega2 = omega * omega;
   if (omega2 < kEpsilon) return (omega2 * radius2) / 3.0 - omega2 / 12.0 + 1.0;
@@ -238,7 +192,7 @@ UD_HD double fov_undistortion_factor(double omega, double radius2) {
 }
 
 // CameraModel::ImgFromCam(u, v, w = 1, check_cheirality = true): w = 1 always has a projectable depth.
-UD_HD bool img_from_normalized(int m, const double* p, double u, double v, double* x, double* y) {
+CAM_HD bool img_from_normalized(int m, const double* p, double u, double v, double* x, double* y) {
   if (m == EQUIRECTANGULAR) {  // models.h:2852-2877 at (u, v, 1): never the zero vector
     const double horizontal = sqrt(u * u + 1.0);
     *x = (atan2(u, 1.0) / (2.0 * kPi) + 0.5) * p[0];
@@ -291,7 +245,7 @@ UD_HD bool img_from_normalized(int m, const double* p, double u, double v, doubl
 // BasePerspectiveCameraModel::IterativeUndistortion (models.h:1141-1197): Newton on x + Distortion(x) = x0 with a trust
 // region, 100 iterations, done when the squared step is below 1e-10. The 2x2 system is solved by elimination with
 // partial pivoting (Eigen's partialPivLu).
-UD_HD bool iterative_undistortion(int m, const double* e, double* u, double* v) {
+CAM_HD bool iterative_undistortion(int m, const double* e, double* u, double* v) {
   const double x0 = *u, y0 = *v;
   double x = x0, y = y0;
   for (int it = 0; it < 100; ++it) {
@@ -329,7 +283,7 @@ UD_HD bool iterative_undistortion(int m, const double* e, double* u, double* v) 
 }
 
 // CameraModel::CamFromImg
-UD_HD bool cam_from_img(int m, const double* p, double x, double y, double* u, double* v) {
+CAM_HD bool cam_from_img(int m, const double* p, double x, double y, double* u, double* v) {
   if (m == EQUIRECTANGULAR) {  // models.h:2883-2903: forward hemisphere only
     const double theta = 2.0 * kPi * (x / p[0] - 0.5);
     const double phi = kPi * (0.5 - y / p[1]);
@@ -395,7 +349,7 @@ UD_HD bool cam_from_img(int m, const double* p, double x, double y, double* u, d
 //   EUCM wants w >= epsilon AND its denominator >= epsilon (:2757-2794),
 //   EQUIRECTANGULAR takes every direction but the zero vector (:2852-2877),
 //   every other model wants HasProjectableDepth(w) = w >= epsilon (:281-285) and then projects (u / w, v / w).
-UD_HD bool img_from_cam(int m, const double* p, double u, double v, double w, double* x, double* y) {
+CAM_HD bool img_from_cam(int m, const double* p, double u, double v, double w, double* x, double* y) {
   if (m == EQUIRECTANGULAR) {
     const double horizontal = sqrt(u * u + w * w);
     if (horizontal + fabs(v) < kEps) return false;
@@ -430,7 +384,7 @@ UD_HD bool img_from_cam(int m, const double* p, double u, double v, double w, do
 
 // CameraModel::CamRayFromImg: the unit bearing of a pixel. EQUIRECTANGULAR covers the whole sphere and always has a
 // value (models.h:813-828); every other model normalises (CamFromImg, 1) (:353-369).
-UD_HD bool cam_ray_from_img(int m, const double* p, double x, double y, double* rx, double* ry, double* rz) {
+CAM_HD bool cam_ray_from_img(int m, const double* p, double x, double y, double* rx, double* ry, double* rz) {
   if (m == EQUIRECTANGULAR) {
     const double theta = 2.0 * kPi * (x / p[0] - 0.5);
     const double phi = kPi * (0.5 - y / p[1]);
@@ -449,5 +403,6 @@ UD_HD bool cam_ray_from_img(int m, const double* p, double x, double y, double* 
   return true;
 }
 
-}  // namespace undistort
-#endif  // COLMAP_AMD_UNDISTORT_MODELS_H_
+}  // namespace camera
+#undef CAM_HD
+#endif  // COLMAP_AMD_CAMERA_PROJECTION_H_

@@ -50,14 +50,14 @@
 #include <vector>
 
 #include "../../include/colmap_amd_obs.h"
+#include "camera_projection.h"
 #include "obs_plan.h"
-#include "undistort_models.h"
 
 #define OBS_API __attribute__((visibility("default")))
 
 namespace {
 
-namespace ud = undistort;
+namespace ud = camera;
 
 thread_local std::string g_error;
 thread_local double g_kernel_ms = 0.0, g_total_ms = 0.0;
@@ -384,12 +384,6 @@ struct Timer {
 
 inline unsigned blocks_for(size_t threads) { return (unsigned)((threads + kBlock - 1) / kBlock); }
 
-void check_model_tables() {  // obs_plan.h validates with a table of its own: the two must describe the same models
-  static_assert(obs_plan::kNumModels == ud::NUM_MODELS && obs_plan::kMaxParams == ud::kMaxParams, "model tables differ");
-  for (int m = 0; m < ud::NUM_MODELS; ++m)
-    if (obs_plan::model_num_params(m) != ud::num_params(m)) throw Fail("obs_plan.h and undistort_models.h disagree on model " + std::to_string(m));
-}
-
 void run(Mode mode, const obs_model* model, const obs_filter_options* options, obs_result* result, int gpu_index) {
   if (!model || !options || !result) throw Fail("null argument");
   const obs_filter_options& opt = *options;
@@ -400,7 +394,6 @@ void run(Mode mode, const obs_model* model, const obs_filter_options* options, o
               "rules must be a combination of OBS_RULE_REPROJ_ERROR and OBS_RULE_TRI_ANGLE");
   }
   if (mode == MODE_SHORT) OBS_CHECK(opt.min_track_len >= 0, "min_track_len must not be negative");
-  check_model_tables();
   obs_plan::validate(*model);
   const obs_model& m = *model;
   bind_device(gpu_index);

@@ -5,6 +5,7 @@
 #ifndef COLMAP_AMD_OBS_PLAN_H_
 #define COLMAP_AMD_OBS_PLAN_H_
 
+#include "../../include/colmap_amd/camera_models.hpp"
 #include "../../include/colmap_amd_obs.h"
 
 #include <algorithm>
@@ -25,15 +26,7 @@ struct Fail : std::runtime_error {
     if (!(cond)) throw ::obs_plan::Fail(std::string("Check failed: ") + (msg)); \
   } while (0)
 
-constexpr int kNumModels = 18;
-constexpr int kMaxParams = 16;
-
-// CameraModel::num_params of colmap::CameraModelId 0 .. 17 (sensor/models.h); -1 for an unknown id. obs_filter.hip
-// compares this table with the one of undistort_models.h before its first launch.
-inline int model_num_params(int model_id) {
-  static const int n[kNumModels] = {3, 4, 4, 5, 8, 8, 12, 5, 4, 5, 12, 16, 4, 5, 3, 4, 6, 2};
-  return model_id >= 0 && model_id < kNumModels ? n[model_id] : -1;
-}
+using colmap_amd::camera_models::kNumModels;
 
 // Lane groups of the per-point pass: a point whose track has up to kSerialMax observations is one lane's work (at most
 // 120 pairs, and the pair loop stops at the first good one); up to kRowMax it gets a row of 16 lanes; a longer track
@@ -68,7 +61,7 @@ inline void validate(const obs_model& m) {
     OBS_CHECK(m.image_camera[i] >= 0 && m.image_camera[i] < m.num_cameras,
               "image " + std::to_string(i) + ": camera index " + std::to_string(m.image_camera[i]) + " out of range");
   for (int32_t c = 0; c < m.num_cameras; ++c) {
-    const int n = model_num_params(m.cameras[c].model_id);
+    const int n = colmap_amd::camera_models::num_params(m.cameras[c].model_id);
     OBS_CHECK(n > 0, "camera " + std::to_string(c) + ": unknown camera model id " + std::to_string(m.cameras[c].model_id));
     OBS_CHECK(m.cameras[c].num_params == n, "camera " + std::to_string(c) + ": model " + std::to_string(m.cameras[c].model_id) +
                                                 " takes " + std::to_string(n) + " parameters, got " +

@@ -10,9 +10,9 @@
 //                                      pitch is padded to whole groups. Source texels are read through the caches:
 //                                      neighbouring lanes read neighbouring texels, nothing is staged in LDS.
 //   undistort_points_kernel            one lane per observation (image/undistortion.cc:334-381)
-//   undistort_resize_kernel<C>         the triangle filter defined in undistort_models.h (indirect path of
+//   undistort_resize_kernel<C>         the triangle filter defined at the kernel (indirect path of
 //                                      WarpImageBetweenCameras, and spherical images with max_image_size)
-// undistort_camera / undistort_cam_from_img are host functions over the same undistort_models.h.
+// undistort_camera / undistort_cam_from_img are host functions over the same camera_projection.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,13 +26,13 @@
 #include <vector>
 
 #include "../../include/colmap_amd_undistort.h"
-#include "undistort_models.h"
+#include "camera_projection.h"
 
 #define UNDISTORT_API __attribute__((visibility("default")))
 
 namespace {
 
-namespace ud = undistort;
+namespace ud = camera;
 
 thread_local std::string g_error;
 thread_local double g_kernel_ms = 0.0, g_total_ms = 0.0;
@@ -191,7 +191,16 @@ undistort_points_kernel(CamArgs distorted, CamArgs undistorted, double* __restri
   xy[2 * i + 1] = y;
 }
 
-// one axis of the triangle filter (undistort_models.h): taps [j0, j1], weight of tap j, for target index i
+// ---- the resize filter (undistort_resize_kernel, the indirect path of WarpImageBetweenCameras) ----
+// The reference shrinks with OpenImageIO's default filter, which is not restated here. This library shrinks with an
+// antialiased separable triangle filter: per axis with s = source size / target size and support r = max(s, 1), target
+// pixel i has its centre at c = (i + 0.5) * s in source coordinates and takes source pixel j (centre j + 0.5) with weight
+// w(j) = max(0, 1 - |j + 0.5 - c| / r) for j = floor(c - r) .. ceil(c + r), restricted to 0 <= j < source size. The value
+// is sum_y wy * (sum_x wx * p(x, y)) divided by (sum_x wx) * (sum_y wy) over the taken pixels (so that a border pixel is
+// a weighted mean of what exists), summed in that order in double, then cast to float, rounded and clamped to [0, 255]
+// like every other pixel (sensor/bitmap.h:216-223). At s = 1 it is the identity; for s <= 1 it is bilinear interpolation.
+//
+// one axis of the filter: taps [j0, j1], weight of tap j, for target index i
 struct Taps {
   int j0, j1;
   double c, r;

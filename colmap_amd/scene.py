@@ -21,38 +21,18 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-# colmap::CameraModelId (sensor/models.h:90-111)
-SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV = 0, 1, 2, 3, 4
-OPENCV_FISHEYE, FULL_OPENCV, FOV, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE, THIN_PRISM_FISHEYE = 5, 6, 7, 8, 9, 10
-SIMPLE_DIVISION, DIVISION, SIMPLE_FISHEYE, FISHEYE, EUCM = 12, 13, 14, 15, 16
-RAD_TAN_THIN_PRISM_FISHEYE, EQUIRECTANGULAR = 11, 17
-MODEL_NAMES = {SIMPLE_PINHOLE: "SIMPLE_PINHOLE", PINHOLE: "PINHOLE", SIMPLE_RADIAL: "SIMPLE_RADIAL", RADIAL: "RADIAL",
-               OPENCV: "OPENCV", OPENCV_FISHEYE: "OPENCV_FISHEYE", FOV: "FOV",
-               SIMPLE_RADIAL_FISHEYE: "SIMPLE_RADIAL_FISHEYE", RADIAL_FISHEYE: "RADIAL_FISHEYE",
-               SIMPLE_DIVISION: "SIMPLE_DIVISION", DIVISION: "DIVISION", SIMPLE_FISHEYE: "SIMPLE_FISHEYE",
-               FISHEYE: "FISHEYE", EUCM: "EUCM", FULL_OPENCV: "FULL_OPENCV",
-               THIN_PRISM_FISHEYE: "THIN_PRISM_FISHEYE", RAD_TAN_THIN_PRISM_FISHEYE: "RAD_TAN_THIN_PRISM_FISHEYE",
-               EQUIRECTANGULAR: "EQUIRECTANGULAR"}
-MODEL_NUM_PARAMS = {SIMPLE_PINHOLE: 3, PINHOLE: 4, SIMPLE_RADIAL: 4, RADIAL: 5, OPENCV: 8,
-                    OPENCV_FISHEYE: 8, FOV: 5, SIMPLE_RADIAL_FISHEYE: 4, RADIAL_FISHEYE: 5,
-                    SIMPLE_DIVISION: 4, DIVISION: 5, SIMPLE_FISHEYE: 3, FISHEYE: 4, EUCM: 6,
-                    FULL_OPENCV: 12, THIN_PRISM_FISHEYE: 12, RAD_TAN_THIN_PRISM_FISHEYE: 16, EQUIRECTANGULAR: 2}
-# FocalLengthIdxs / PrincipalPointIdxs / ExtraParamsIdxs (sensor/models.h)
-_ONE_F = (SIMPLE_PINHOLE, SIMPLE_RADIAL, RADIAL, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE, SIMPLE_DIVISION, SIMPLE_FISHEYE)
-MODEL_FOCAL_IDXS = {m: ([0] if m in _ONE_F else [0, 1]) for m in MODEL_NUM_PARAMS}
-MODEL_PP_IDXS = {m: ([1, 2] if m in _ONE_F else [2, 3]) for m in MODEL_NUM_PARAMS}
-MODEL_EXTRA_IDXS = {m: list(range(3 if m in _ONE_F else 4, n)) for m, n in MODEL_NUM_PARAMS.items()}
-# EQUIRECTANGULAR: (width, height) are metadata parameters, never refined (MetaDataParamsIdxs, models.h:2839-2842)
-MODEL_FOCAL_IDXS[EQUIRECTANGULAR] = MODEL_PP_IDXS[EQUIRECTANGULAR] = MODEL_EXTRA_IDXS[EQUIRECTANGULAR] = []
+from .camera import MODELS, Camera  # noqa: F401  (Camera is this module's camera class)
 
-
-@dataclass
-class Camera:
-    camera_id: int
-    model_id: int
-    width: int
-    height: int
-    params: np.ndarray  # float64
+# colmap::CameraModelId (sensor/models.h:90-111): the eighteen ids by name, and the tables of camera.MODELS by id
+(SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, FULL_OPENCV, FOV, SIMPLE_RADIAL_FISHEYE,
+ RADIAL_FISHEYE, THIN_PRISM_FISHEYE, RAD_TAN_THIN_PRISM_FISHEYE, SIMPLE_DIVISION, DIVISION, SIMPLE_FISHEYE, FISHEYE, EUCM,
+ EQUIRECTANGULAR) = range(len(MODELS))
+assert all(globals()[m.name] == i for i, m in enumerate(MODELS))
+MODEL_NAMES = {i: m.name for i, m in enumerate(MODELS)}
+MODEL_NUM_PARAMS = {i: m.num_params for i, m in enumerate(MODELS)}
+MODEL_FOCAL_IDXS = {i: list(m.focal_length_idxs) for i, m in enumerate(MODELS)}
+MODEL_PP_IDXS = {i: list(m.principal_point_idxs) for i, m in enumerate(MODELS)}
+MODEL_EXTRA_IDXS = {i: list(m.extra_params_idxs) for i, m in enumerate(MODELS)}
 
 
 @dataclass

@@ -13,13 +13,14 @@ from __future__ import annotations
 import ctypes as C
 import os
 import shutil
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
 from . import workspace as W
+from .camera import model as camera_model
 
 EQUIRECTANGULAR = W.CAMERA_MODEL_IDS["EQUIRECTANGULAR"]
 PINHOLE = W.CAMERA_MODEL_IDS["PINHOLE"]
@@ -118,7 +119,10 @@ def IsUndistorted(cam) -> bool:
     """Camera::IsUndistorted (scene/camera.cc:98-111): spherical, or every extra parameter within 1e-8 of zero."""
     if IsSpherical(cam):
         return True
-    first_extra = max(W.CAMERA_MODELS[cam.model_id][4:6]) + 1
+    m = camera_model(cam.model_id)
+    if m is None:
+        raise KeyError(cam.model_id)
+    first_extra = len(m.focal_length_idxs) + len(m.principal_point_idxs)
     return not np.any(np.abs(np.asarray(cam.params, np.float64)[first_extra:]) > 1e-8)
 
 
@@ -207,7 +211,7 @@ def UndistortPoints(distorted_camera, undistorted_camera, xy: np.ndarray, gpu_in
 
 
 def ResizeBitmap(bitmap: np.ndarray, width: int, height: int, gpu_index: int = 0) -> np.ndarray:
-    """Bitmap::Rescale with the library's triangle filter (colmap_amd/csrc/undistort_models.h), on the GPU."""
+    """Bitmap::Rescale with the library's triangle filter (colmap_amd/csrc/undistort.hip), on the GPU."""
     bmp = np.ascontiguousarray(bitmap, np.uint8)
     ch = 1 if bmp.ndim == 2 else bmp.shape[2]
     out = np.empty((height, width) + (() if bmp.ndim == 2 else (ch,)), np.uint8)
@@ -230,8 +234,7 @@ def UndistortReconstruction(options: UndistortCameraOptions, model: W.SparseMode
     def keep_unchanged(cam):  # :316-318
         return IsUndistorted(cam) and options.max_image_size < 0
 
-    distorted = {cid: W.SparseCamera(c.camera_id, c.model_id, c.width, c.height, np.array(c.params, np.float64))
-                 for cid, c in model.cameras.items()}
+    distorted = {cid: replace(c, params=np.array(c.params, np.float64)) for cid, c in model.cameras.items()}
     for cid, cam in distorted.items():
         if keep_unchanged(cam):
             continue

@@ -19,48 +19,14 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .camera import MODELS, Camera as SparseCamera  # noqa: F401  (the camera class of the sparse-model readers)
+
 # colmap::CameraModelId -> (name, number of parameters, fx index, fy index, cx index, cy index)
-# (sensor/models.h:90-111 and the FocalLengthIdxs / PrincipalPointIdxs of each model)
-CAMERA_MODELS = {
-    0: ("SIMPLE_PINHOLE", 3, 0, 0, 1, 2),
-    1: ("PINHOLE", 4, 0, 1, 2, 3),
-    2: ("SIMPLE_RADIAL", 4, 0, 0, 1, 2),
-    3: ("RADIAL", 5, 0, 0, 1, 2),
-    4: ("OPENCV", 8, 0, 1, 2, 3),
-    5: ("OPENCV_FISHEYE", 8, 0, 1, 2, 3),
-    6: ("FULL_OPENCV", 12, 0, 1, 2, 3),
-    7: ("FOV", 5, 0, 1, 2, 3),
-    8: ("SIMPLE_RADIAL_FISHEYE", 4, 0, 0, 1, 2),
-    9: ("RADIAL_FISHEYE", 5, 0, 0, 1, 2),
-    10: ("THIN_PRISM_FISHEYE", 12, 0, 1, 2, 3),
-    11: ("RAD_TAN_THIN_PRISM_FISHEYE", 16, 0, 1, 2, 3),
-    12: ("SIMPLE_DIVISION", 4, 0, 0, 1, 2),
-    13: ("DIVISION", 5, 0, 1, 2, 3),
-    14: ("SIMPLE_FISHEYE", 3, 0, 0, 1, 2),
-    15: ("FISHEYE", 4, 0, 1, 2, 3),
-    16: ("EUCM", 6, 0, 1, 2, 3),
-    17: ("EQUIRECTANGULAR", 2, None, None, None, None),  # width, height: no focal length / principal point
-}
+# (one focal length serves both axes; None where EQUIRECTANGULAR has no focal length / principal point)
+CAMERA_MODELS = {i: (m.name, m.num_params) + ((m.focal_length_idxs[0], m.focal_length_idxs[-1], *m.principal_point_idxs)
+                                              if m.focal_length_idxs else (None,) * 4) for i, m in enumerate(MODELS)}
 CAMERA_MODEL_IDS = {v[0]: k for k, v in CAMERA_MODELS.items()}
 INVALID_POINT3D = 0xFFFFFFFFFFFFFFFF  # kInvalidPoint3DId (util/types.h)
-
-
-@dataclass
-class SparseCamera:
-    camera_id: int
-    model_id: int
-    width: int
-    height: int
-    params: np.ndarray
-
-    def CalibrationMatrix(self) -> np.ndarray:
-        """Camera::CalibrationMatrix (scene/camera.cc:63-72)."""
-        _, _, ifx, ify, icx, icy = CAMERA_MODELS[self.model_id]
-        if ifx is None:
-            raise ValueError(f"{CAMERA_MODELS[self.model_id][0]} cameras have no calibration matrix")
-        K = np.eye(3)
-        K[0, 0], K[1, 1], K[0, 2], K[1, 2] = self.params[ifx], self.params[ify], self.params[icx], self.params[icy]
-        return K
 
 
 @dataclass

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../colmap_amd_ba.h"
+#include "camera.hpp"
 
 namespace colmap_amd {
 
@@ -104,46 +105,27 @@ inline Rigid3d Compose(const Rigid3d& a, const Rigid3d& b) {
   return out;
 }
 
-// CameraModelId (sensor/models.h:90-111): the models the MI355X backend supports.
-enum class CameraModelId : int {
-  SIMPLE_PINHOLE = 0, PINHOLE = 1, SIMPLE_RADIAL = 2, RADIAL = 3, OPENCV = 4,
-  OPENCV_FISHEYE = 5, FULL_OPENCV = 6, FOV = 7, SIMPLE_RADIAL_FISHEYE = 8, RADIAL_FISHEYE = 9,
-  THIN_PRISM_FISHEYE = 10, RAD_TAN_THIN_PRISM_FISHEYE = 11, SIMPLE_DIVISION = 12, DIVISION = 13, SIMPLE_FISHEYE = 14, FISHEYE = 15, EUCM = 16,
-  EQUIRECTANGULAR = 17
-};
-
+// CameraModelId is the enum of camera_models.hpp; every model of its table is supported.
 struct CameraModelInfo {
   int num_params;
   std::vector<size_t> focal_length_idxs, principal_point_idxs, extra_params_idxs;
 };
 
+// FocalLengthIdxs / PrincipalPointIdxs / ExtraParamsIdxs of a model; null for an id that is not a model.
 inline const CameraModelInfo* GetCameraModelInfo(int model_id) {
-  static const CameraModelInfo kSimplePinhole{3, {0}, {1, 2}, {}}, kPinhole{4, {0, 1}, {2, 3}, {}},
-      kSimpleRadial{4, {0}, {1, 2}, {3}}, kRadial{5, {0}, {1, 2}, {3, 4}}, kOpenCV{8, {0, 1}, {2, 3}, {4, 5, 6, 7}},
-      kTwoFocalOneExtra{5, {0, 1}, {2, 3}, {4}}, kEucm{6, {0, 1}, {2, 3}, {4, 5}},
-      kTwelve{12, {0, 1}, {2, 3}, {4, 5, 6, 7, 8, 9, 10, 11}},
-      kSixteen{16, {0, 1}, {2, 3}, {4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}}, kEquirectangular{2, {}, {}, {}};
-  switch (model_id) {
-    case 0: case 14: return &kSimplePinhole;  // SIMPLE_PINHOLE, SIMPLE_FISHEYE: f cx cy
-    case 1: case 15: return &kPinhole;        // PINHOLE, FISHEYE: fx fy cx cy
-    case 2: case 8: case 12: return &kSimpleRadial;  // SIMPLE_RADIAL, SIMPLE_RADIAL_FISHEYE, SIMPLE_DIVISION: f cx cy k
-    case 3: case 9: return &kRadial;         // RADIAL, RADIAL_FISHEYE: f cx cy k1 k2
-    case 4: case 5: return &kOpenCV;         // OPENCV, OPENCV_FISHEYE: fx fy cx cy + four extra
-    case 7: case 13: return &kTwoFocalOneExtra;  // FOV (omega), DIVISION (k): fx fy cx cy + one extra
-    case 16: return &kEucm;                  // EUCM: fx fy cx cy alpha beta
-    case 11: return &kSixteen;               // RAD_TAN_THIN_PRISM_FISHEYE: k0..k5 p0 p1 s0..s3
-    case 17: return &kEquirectangular;       // EQUIRECTANGULAR: width height, metadata only (never refined)
-    case 6: case 10: return &kTwelve;        // FULL_OPENCV (k1 k2 p1 p2 k3 k4 k5 k6), THIN_PRISM_FISHEYE (k1 k2 p1 p2 k3 k4 sx1 sy1)
-    default: return nullptr;
-  }
+  static const std::vector<CameraModelInfo> infos = [] {
+    std::vector<CameraModelInfo> v;
+    for (const camera_models::ModelInfo& k : camera_models::kModels) {
+      v.push_back({k.num_params, {}, {}, {}});
+      if (k.num_focal() >= 1) v.back().focal_length_idxs.push_back(k.fx);
+      if (k.num_focal() == 2) v.back().focal_length_idxs.push_back(k.fy);
+      if (k.cx >= 0) v.back().principal_point_idxs = {static_cast<size_t>(k.cx), static_cast<size_t>(k.cy)};
+      for (int j = k.first_extra; j < k.num_params; ++j) v.back().extra_params_idxs.push_back(j);
+    }
+    return v;
+  }();
+  return camera_models::model_info(model_id) ? &infos[static_cast<size_t>(model_id)] : nullptr;
 }
-
-struct Camera {  // scene/camera.h
-  camera_t camera_id = 0;
-  int model_id = static_cast<int>(CameraModelId::SIMPLE_RADIAL);
-  size_t width = 0, height = 0;
-  std::vector<double> params;
-};
 
 struct Point2D {  // scene/point2d.h
   std::array<double, 2> xy{0, 0};

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../colmap_amd_obs.h"
+#include "camera.hpp"
 
 namespace colmap_amd {
 namespace obs {
@@ -30,11 +31,7 @@ enum class ReprojectionErrorType { PIXEL = OBS_ERROR_PIXEL, NORMALIZED = OBS_ERR
 
 constexpr int64_t kInvalidPoint3DId = -1;
 
-struct Camera {  // scene/camera.h: model_id is colmap::CameraModelId
-  int model_id = 0;
-  int width = 0, height = 0;
-  std::vector<double> params;
-};
+using Camera = ::colmap_amd::Camera;
 
 struct Point2D {
   double xy[2] = {0.0, 0.0};

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../colmap_amd_undistort.h"
+#include "camera.hpp"
 
 namespace colmap_amd {
 
@@ -38,21 +39,6 @@ struct UndistortCameraOptions {  // image/undistortion.h:38-71
   double max_cam_point_norm = -1;
   WarpImageOptions warp_options;
   int gpu_index = 0;  // (MI355X) the device the pixels and observations are computed on
-};
-
-struct Camera {  // scene/camera.h: model_id is colmap::CameraModelId
-  int model_id = 0;
-  int width = 0, height = 0;
-  std::vector<double> params;
-  bool IsSpherical() const { return model_id == 17; }
-  bool IsUndistorted() const {  // scene/camera.cc:98-111
-    if (IsSpherical()) return true;
-    const bool one_f = model_id == 0 || model_id == 2 || model_id == 3 || model_id == 8 || model_id == 9 ||
-                       model_id == 12 || model_id == 14;
-    for (size_t i = one_f ? 3 : 4; i < params.size(); ++i)
-      if (std::abs(params[i]) > 1e-8) return false;
-    return true;
-  }
 };
 
 struct Bitmap {  // 8-bit grey (channels 1) or RGB (channels 3), rows tight
@@ -86,12 +72,14 @@ inline undistort_cam ToC(const Camera& cam) {
   for (size_t i = 0; i < cam.params.size(); ++i) c.params[i] = cam.params[i];
   return c;
 }
-inline Camera FromC(const undistort_cam& c, size_t num_params) {
+inline Camera FromC(const undistort_cam& c) {  // of a camera the library wrote: a known model
   Camera cam;
   cam.model_id = c.model_id;
   cam.width = c.width;
   cam.height = c.height;
-  cam.params.assign(c.params, c.params + num_params);
+  const camera_models::ModelInfo* info = camera_models::model_info(c.model_id);
+  if (!info) throw std::runtime_error("unknown camera model id " + std::to_string(c.model_id));
+  cam.params.assign(c.params, c.params + info->num_params);
   return cam;
 }
 inline void Check(int rc) {
@@ -105,7 +93,7 @@ inline Camera UndistortCamera(const UndistortCameraOptions& options, const Camer
   const undistort_cam c = undistort_detail::ToC(camera);
   undistort_cam u;
   undistort_detail::Check(undistort_camera(&o, &c, &u));
-  return undistort_detail::FromC(u, 4);  // PINHOLE
+  return undistort_detail::FromC(u);
 }
 
 // UndistortImage (image/undistortion.cc:266-301) on device options.gpu_index.
@@ -127,7 +115,7 @@ inline void UndistortImage(const UndistortCameraOptions& options, const Bitmap& 
   im.out = undistorted_bitmap->data.data();
   im.out_capacity = cap;
   undistort_detail::Check(undistort_images(&o, 1, &im, options.gpu_index));
-  *undistorted_camera = undistort_detail::FromC(im.out_camera, distorted_camera.IsSpherical() ? 2 : 4);
+  *undistorted_camera = undistort_detail::FromC(im.out_camera);
   undistorted_bitmap->width = im.out_camera.width;
   undistorted_bitmap->height = im.out_camera.height;
   undistorted_bitmap->channels = distorted_bitmap.channels;

@@ -207,7 +207,8 @@ void ba_options_init(ba_options* options);
 int ba_solve_sharded(ba_problem* problem, const ba_options* options, int32_t gpu_index, const ba_comm* comm,
                      ba_result* result);
 /* Number of observations rank `rank` of `world_size` works on (host-only helper, no GPU needed):
- * active observations (>= 1 variable block) whose pose index satisfies pose % world_size == rank. */
+ * active observations (>= 1 variable block) whose pose index satisfies pose % world_size == rank.
+ * -1 for a null problem, a rank outside the world, or a camera whose model id is not a camera model. */
 int64_t ba_shard_num_observations(const ba_problem* problem, int32_t rank, int32_t world_size);
 /* The same for BA_SHARD_BY_POINT (point % world_size == rank). */
 int64_t ba_shard_num_observations_by_point(const ba_problem* problem, int32_t rank, int32_t world_size);

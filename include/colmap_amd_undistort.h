@@ -11,7 +11,7 @@
  * the file reading and writing of controllers/undistorters.cc. Pixels and observations are computed on the GPU
  * (colmap_amd/csrc/undistort.hip); there is no CPU path for them. All geometry is double precision.
  * Difference to the reference: the indirect path (target much smaller than the source) and the resize of spherical
- * images shrink with the triangle filter defined in colmap_amd/csrc/undistort_models.h, not OpenImageIO's.
+ * images shrink with the triangle filter defined in colmap_amd/csrc/undistort.hip, not OpenImageIO's.
  */
 #ifndef COLMAP_AMD_UNDISTORT_H_
 #define COLMAP_AMD_UNDISTORT_H_
@@ -83,7 +83,7 @@ int undistort_images(const undistort_options* options, int32_t num_images, undis
 int undistort_points(const undistort_cam* distorted, const undistort_cam* undistorted, double* xy, int64_t n,
                      int32_t gpu_index);
 
-/* Bitmap::Rescale as this library does it (the triangle filter of colmap_amd/csrc/undistort_models.h) on device
+/* Bitmap::Rescale as this library does it (the triangle filter of colmap_amd/csrc/undistort.hip) on device
  * gpu_index: src [src_height][src_width][channels] -> dst [dst_height][dst_width][channels]. 0 = ok. */
 int undistort_resize(const uint8_t* src, int32_t src_width, int32_t src_height, int32_t channels, uint8_t* dst,
                      int32_t dst_width, int32_t dst_height, int32_t gpu_index);

@@ -34,7 +34,8 @@ def _emul_lib():
         deps = [os.path.join(_CSRC, f) for f in ("ba_kernels.hip", "ba_schur_explicit.hip", "ba_schur_explicit.h", "ba_layout.h",
                                                    "ba_probe.h")]
         deps += [os.path.join(_HERE, "hip", "hip_runtime.h"), os.path.join(_HERE, "rccl", "rccl.h"),
-                 os.path.join(_HERE, "build_ba.sh"), os.path.join(os.path.dirname(_HERE), "..", "include", "colmap_amd_ba.h")]
+                 os.path.join(_HERE, "build_ba.sh"), os.path.join(os.path.dirname(_HERE), "..", "include", "colmap_amd_ba.h"),
+                 os.path.join(os.path.dirname(_HERE), "..", "include", "colmap_amd", "camera_models.hpp")]
         if not os.path.exists(path) or any(os.path.getmtime(d) > os.path.getmtime(path) for d in deps):
             subprocess.check_call(["sh", os.path.join(_HERE, "build_ba.sh")])
         _LIB = C.CDLL(path)

@@ -20,8 +20,9 @@ def _emul_lib():
     global _lib
     if _lib is None:
         so, src = os.path.join(EMUL, "libobs_emul.so"), os.path.join(EMUL, "..", "..", "colmap_amd", "csrc")
-        deps = [os.path.join(src, f) for f in ("obs_filter.hip", "obs_plan.h", "undistort_models.h")]
-        deps += [os.path.join(EMUL, "hip", "hip_runtime.h"), os.path.join(EMUL, "..", "..", "include", "colmap_amd_obs.h")]
+        deps = [os.path.join(src, f) for f in ("obs_filter.hip", "obs_plan.h", "camera_projection.h")]
+        deps += [os.path.join(EMUL, "hip", "hip_runtime.h"), os.path.join(EMUL, "..", "..", "include", "colmap_amd_obs.h"),
+                 os.path.join(EMUL, "..", "..", "include", "colmap_amd", "camera_models.hpp")]
         if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
             subprocess.check_call(["sh", os.path.join(EMUL, "build_obs.sh")])
         _lib = C.CDLL(so)

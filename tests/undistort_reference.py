@@ -344,7 +344,7 @@ def warp(source_cam, target_cam, image, interpolation="bilinear", half_tol=1e-4,
 
 
 def _resize_weights(src_size, dst_size):
-    """The triangle filter of colmap_amd/csrc/undistort_models.h as a (dst, src) matrix of unnormalised weights."""
+    """The triangle filter of colmap_amd/csrc/undistort.hip as a (dst, src) matrix of unnormalised weights."""
     s = src_size / dst_size
     r = max(s, 1.0)
     c = (np.arange(dst_size, dtype=np.float64) + 0.5) * s
