@@ -345,7 +345,8 @@ struct pm_handle {
   DevBuf<uint32_t> src_fp_off;       // [S] the packed source images as slots of the problem's buffer resource
   const uint32_t* fp_base = nullptr; // its base (lowest address among them); null: the images lie too far apart
   const char* sweep_kernel = "";     // kernel of the last sweep launch (pm_get_sweep_kernel_name)
-  DevBuf<unsigned long long> evals;  // NCC evaluations of the sweep launches of the last run
+  DevBuf<unsigned long long> evals;  // [3] last run: NCC evaluations of the sweep launches; of them answered without taps;
+                                     // evaluations of the initial cost answered without taps (PmParams::answered)
   DevBuf<PmParams> plan;  // per-launch parameter blocks of the last (batched) run
   hipStream_t run_stream = nullptr;  // stream the last run was enqueued on
   PmParams base;
@@ -636,8 +637,9 @@ void Create(const pm_options& opt_in, const pm_problem& prob, pm_image_cache* ca
     h->mask.alloc((size_t)S * W * H);
     b.mask = h->mask.ptr;
   }
-  h->evals.alloc(1);
+  h->evals.alloc(3);
   b.evals = h->evals.ptr;
+  b.answered = h->evals.ptr + 1;
   h->out_depth.alloc((size_t)W * H);
   h->out_normal.alloc((size_t)3 * W * H);
   h->out_sel.alloc((size_t)S * W * H);
@@ -729,7 +731,7 @@ void RunBatchAsync(pm_handle** hs, int n, hipStream_t run_st = nullptr) {
     if (h->mask.ptr) HIP_CALL(hipMemsetAsync(h->mask.ptr, 0, h->mask.count, st));
     if (h->prof.ptr)
       HIP_CALL(hipMemsetAsync(h->prof.ptr, 0, kPmProfSlots * sizeof(unsigned long long), st));
-    HIP_CALL(hipMemsetAsync(h->evals.ptr, 0, sizeof(unsigned long long), st));
+    HIP_CALL(hipMemsetAsync(h->evals.ptr, 0, 3 * sizeof(unsigned long long), st));
   }
   pm_launch_initial_cost(run_plan, h0->plan.ptr, n, st);
   for (int k = 0; k < limit; ++k) {
@@ -1218,6 +1220,17 @@ int pm_get_evaluation_count(pm_handle* h, unsigned long long* sweep_evals, unsig
     if (sweep_evals)
       HIP_CALL(hipMemcpy(sweep_evals, h->evals.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (initial_evals) *initial_evals = (unsigned long long)h->W * h->H * h->S;  // ComputeInitialCost
+  });
+}
+
+int pm_get_answered_count(pm_handle* h, unsigned long long* sweep_answered, unsigned long long* initial_answered) {
+  return Guard([&] {
+    PM_CHECK(h && h->ran, "pm_run must be called first");
+    HIP_CALL(hipSetDevice(h->device));
+    unsigned long long both[2];
+    HIP_CALL(hipMemcpy(both, h->evals.ptr + 1, sizeof(both), hipMemcpyDeviceToHost));
+    if (sweep_answered) *sweep_answered = both[0];
+    if (initial_answered) *initial_answered = both[1];
   });
 }
 

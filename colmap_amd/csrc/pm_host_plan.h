@@ -99,6 +99,8 @@ struct PmParams {
   unsigned long long* prof; // optional phase-cycle counters [kPmProfSlots] (debug), else null
   unsigned long long* evals; // NCC evaluations executed by the sweep kernels of this run (one atomic
                              // add per workgroup at its end), always allocated
+  unsigned long long* answered; // [2] of them the 11 x 11 wave kernels answered without taps (pm_patch_class.h): by the
+                                // sweep kernels, by the initial cost; one atomic add per wave at its end
   unsigned long long* trace; // optional progress trace (debug, pm_enable_progress_trace): [column group][row / 128]
                              // device-wide clock when the group's wave reached that row, last sweep launch; else null
   int trace_stride;          // samples per column group

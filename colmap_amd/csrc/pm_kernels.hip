@@ -31,6 +31,7 @@
 // Arithmetic is specified in oracle/pm_oracle.c (header) and implemented here
 // independently; compile with -ffp-contract=off.
 #include "pm_internal.h"
+#include "pm_patch_class.h"  // patch_inside, patch_answered: the classes of an NCC task
 
 #include "gfx950/pm_gfx950_asm.h"  // ubyte0..3, reduce16x3, launder_vgpr, llvm_struct_buffer_load_u32 (see its header)
 
@@ -1716,36 +1717,7 @@ __device__ __forceinline__ void patch_weights_wave(const PmParams& p, const Lds&
   }
 }
 
-// Does every tap of the patch with (centred) homography Hm provably fall on texels x in [0, w - 1],
-// y in [0, h - 1] of the source image? The window maps to a convex quadrilateral when the projective
-// divisor is positive at its four corners, so the taps lie inside the corners' bounding box; one
-// texel of margin absorbs the rounding of the per-tap evaluation. NaNs compare false.
-__device__ __forceinline__ bool patch_inside(const PmParams& p, const float Hm[9]) {
-  // With z > 0 at a corner, 1 <= x / z <= w - 2 is z <= x <= (w - 2) z: eight divisions saved per task. The
-  // flag only selects the addressing variant of the gathers (both give the same texels for a patch that is
-  // inside; the one-texel margin dwarfs the rounding of the products), it never changes a result -- so the corner
-  // values are taken incrementally (two products and three sums per coordinate instead of eight and eight).
-  const float e = (float)(2 * p.radius);  // window extent: taps at offsets 0 .. 2 r
-  const float wx = (float)(p.src_w - 2), wy = (float)(p.src_h - 2);
-  float x[4], y[4], z[4];
-  {
-    const float a = Hm[0] * e, b = Hm[1] * e;
-    x[0] = Hm[2]; x[1] = a + x[0]; x[2] = b + x[0]; x[3] = a + x[2];
-  }
-  {
-    const float a = Hm[3] * e, b = Hm[4] * e;
-    y[0] = Hm[5]; y[1] = a + y[0]; y[2] = b + y[0]; y[3] = a + y[2];
-  }
-  {
-    const float a = Hm[6] * e, b = Hm[7] * e;
-    z[0] = Hm[8]; z[1] = a + z[0]; z[2] = b + z[0]; z[3] = a + z[2];
-  }
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    ok = ok && (z[k] > 0.0f) && x[k] >= z[k] && y[k] >= z[k] && x[k] <= wx * z[k] && y[k] <= wy * z[k];
-  return ok;
-}
+// (patch_inside, patch_answered: pm_patch_class.h)
 
 // Synchronisation point between the lane-parallel phases of ONE wave. A single-wave workgroup's
 // __syncthreads() compiles to the two fences without an s_barrier; the multi-wave workgroup spells that out so
@@ -1762,44 +1734,87 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 // Position of lane `tid`'s task in the batch's pass-B order: the tasks whose patch is inside the source image
-// (`m1`: their lanes) first, each class in lane order; `n` = lanes that hold a task.
-__device__ __forceinline__ int batch_position(unsigned long long m1, int n, int tid, bool inside) {
+// (`m1`: their lanes) first, then the clamped ones, then the answered ones (`m2`: their lanes and the padding's), each
+// class in lane order; `n` = lanes that hold a task or padding. The lane's own class is read from the masks.
+__device__ __forceinline__ int batch_position(unsigned long long m1, unsigned long long m2, int n, int tid) {
   const unsigned long long valid = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
-  const unsigned long long m0 = valid & ~m1;
-  return inside ? lanes_below(m1) : __popcll(m1) + lanes_below(m0);
+  const unsigned long long m0 = valid & ~(m1 | m2);
+  if ((m1 >> tid) & 1ull) return lanes_below(m1);
+  if ((m2 >> tid) & 1ull) return n - __popcll(m2) + lanes_below(m2);
+  return __popcll(m1) + lanes_below(m0);
 }
+
+// The class of lane `tid`'s task, end of pass A (every lane of the wave calls this): `real` = the lane holds a task,
+// `pad` = it holds padding, which counts as answered so that it sorts behind every task. patch_answered
+// (pm_patch_class.h) in two steps: the flat-reference rule is three instructions, and the outside rule is evaluated only
+// when some task of the batch is neither flat nor inside -- a wave-uniform branch that the batches of an image's
+// interior, all inside, do not take. An answered task is never `inside`: the classes are disjoint.
+__device__ __forceinline__ void task_class(const PmParams& p, const float Hm[9], bool real, bool pad, float ref_sum,
+                                           float ref_sqsum, bool& inside, bool& answered) {
+  const bool flat = real && ref_flat(ref_sum, ref_sqsum);
+  inside = real && !flat && patch_inside(p, Hm);
+  answered = pad || flat;
+  const bool open = real && !flat && !inside;
+  if (__ballot(open ? 1 : 0) != 0ull) answered = answered || (open && patch_outside(p, Hm));
+}
+
+// What pass B runs of a published batch: `rounds` rounds of four positions, the first `fast` of them unclamped; sums
+// are stored for positions below `nb` (not the padding).
+struct BatchRounds {
+  int nb, rounds, fast;
+};
 
 // End of pass A, lane per task: everything pass B needs to know about a task goes to the task's position in the
 // batch's order, in the form pass B consumes (kSlotWords). Order: the tasks whose patch is inside the source image
-// first. A round takes the cheaper unclamped addressing only when all four of its patches are inside; with the tasks
-// in list order one outside patch in four spoils the round, sorted they collect in the last rounds, and rounds
-// 0 .. n_inside / 4 - 1 are the unclamped ones: a scalar comparison in pass B. Results are stored per task, so the
-// order cannot change a bit. The batch is padded to whole rounds: lanes nb .. nb4 - 1 bring a copy of the batch's last
-// task with `inside` false, which lands behind every real task, is evaluated with clamped addresses and never stored.
-// Returns n_inside; `m1` = the lanes of the inside tasks (batch_position of the finishing lane).
+// first, the answered ones (pm_patch_class.h: their three sums are +0, or their cost is 2.0f whatever the sums) last. A
+// round takes the cheaper unclamped addressing only when all four of its patches are inside; with the tasks in list
+// order one outside patch in four spoils the round, sorted they collect in the last rounds, and rounds
+// 0 .. n_inside / 4 - 1 are the unclamped ones: a scalar comparison in pass B. Pass B runs only the rounds that hold a
+// task that is not answered, ceil((nb - n_answered) / 4): the positions behind them get +0 sums here, in place of their
+// homography, and are never evaluated; an answered task that shares the last running round with a clamped one is simply
+// evaluated. Results are stored per task, so the order cannot change a bit. The batch is padded to whole rounds: lanes
+// nb .. nb4 - 1 bring a copy of the batch's last task in the answered class, which lands behind every real task, is
+// evaluated with clamped addresses if its round runs at all and never stored.
+// `m1`, `m2` = the lanes of the inside and of the answered tasks (batch_position of the finishing lane).
 template <bool MUBUF>
-__device__ __forceinline__ int batch_publish(const PmParams& p, const Lds& L, int tid, int nb4, bool inside,
-                                             const float Hm[9], int c, int s, unsigned long long& m1) {
+__device__ __forceinline__ BatchRounds batch_publish(const PmParams& p, const Lds& L, int tid, int nb, int nb4, bool inside,
+                                                     bool answered, const float Hm[9], int c, int s,
+                                                     unsigned long long& m1, unsigned long long& m2) {
   m1 = __ballot(inside ? 1 : 0);
+  m2 = __ballot(answered ? 1 : 0);
   const int n_inside = __popcll(m1);
+  const int n_run = nb4 - __popcll(m2);  // tasks that must be evaluated (m2 holds the padding lanes too)
+  BatchRounds br;
+  br.nb = nb;
+  br.rounds = (n_run + 3) >> 2;
+  br.fast = n_inside >> 2;
   if (tid < nb4) {
-    const int pos = batch_position(m1, nb4, tid, inside);
+    const int pos = batch_position(m1, m2, nb4, tid);
     lds_f32* slot = L.th + pos * kSlotWords;
-    for (int k = 0; k < 9; ++k) slot[k] = Hm[k];
-    uint32_t img = (uint32_t)s | ((uint32_t)c << 16);
-    if (MUBUF) {
-      img = L.fpo[s] | (uint32_t)c;
-      // slot offset of texel (0, 0) relative to entry (0, 0): one strip (kFpRingX entries) and kFpRingY rows
-      if (pos < (n_inside & ~3)) img += 4u * ((uint32_t)p.fp_rows1 + 1u) + 4u * (uint32_t)kFpRingY;
+    if (pos < 4 * br.rounds) {
+      for (int k = 0; k < 9; ++k) slot[k] = Hm[k];
+      uint32_t img = (uint32_t)s | ((uint32_t)c << 16);
+      if (MUBUF) {
+        img = L.fpo[s] | (uint32_t)c;
+        // slot offset of texel (0, 0) relative to entry (0, 0): one strip (kFpRingX entries) and kFpRingY rows
+        if (pos < (n_inside & ~3)) img += 4u * ((uint32_t)p.fp_rows1 + 1u) + 4u * (uint32_t)kFpRingY;
+      }
+      ((lds_u32*)slot)[9] = img;
+    } else {
+      slot[0] = 0.0f;  // answered: the three window sums
+      slot[1] = 0.0f;
+      slot[2] = 0.0f;
     }
-    ((lds_u32*)slot)[9] = img;
   }
-  return n_inside;
+  return br;
 }
 
+// Tasks of a batch that pass B never touches (the answered-without-taps counter; wave-uniform)
+__device__ __forceinline__ int batch_skipped(const BatchRounds& br) { return br.nb - min(br.nb, 4 * br.rounds); }
+
 // Mailbox of a wave pair (pm_sweep_pair_kernel): the words behind Lds::best[C] -- its 16-byte slot holds C <= 2 entries,
-// the pair kernel runs one column per group -- carry the size of the published batch (nb | n_inside << 8) and whether
-// it is the phase's last.
+// the pair kernel runs one column per group -- carry the published batch (nb | unclamped rounds << 8 | rounds << 16:
+// BatchRounds) and whether it is the phase's last.
 constexpr int kPairNb = 2, kPairLast = 3;
 
 // Pass B of a batch of NCC tasks, 16-lane group per task: one round = four tasks; all eight gathers of a lane are in
@@ -1810,13 +1825,13 @@ constexpr int kPairNb = 2, kPairLast = 3;
 // (its group's position, linear in the round) for homography and record; the sums of a task replace its homography.
 template <bool MUBUF>
 __device__ __forceinline__ void ncc_rounds_wave(const PmParams& p, const Lds& L, const v4i srd, const lds_f32* G, int tid,
-                                                int nb, int n_inside, int first, int stride) {
+                                                const BatchRounds br, int first, int stride) {
   const int g = tid >> 4, j = tid & 15;
   const uint32_t gorigin = fp_index(kFpRingX, kFpRingY, (unsigned)p.fp_rows1);  // texel (0, 0) as an entry index
-  const int rounds = (nb + 3) >> 2;
-  const int fast_rounds = n_inside >> 2;  // wave-uniform: the unclamped addressing when all four patches are inside
+  const int rounds = br.rounds;     // (answered tasks behind the last of them are never evaluated: batch_publish)
+  const int fast_rounds = br.fast;  // wave-uniform: the unclamped addressing when all four patches are inside
   const lds_f32* H = L.th + (g + 4 * first) * kSlotWords;
-  const lds_f32* const end = L.th + nb * kSlotWords;
+  const lds_f32* const end = L.th + br.nb * kSlotWords;
   const lds_f32* wj = L.wgt + j;   // this lane's taps of column 0: one register each, whole (not a base + constant
   const lds_f32* rj = L.refc + j;  // that every round would add again)
   launder_lds(wj);
@@ -1848,10 +1863,11 @@ __device__ __forceinline__ void ncc_rounds_wave(const PmParams& p, const Lds& L,
 // Run the `n` queued NCC tasks (and, with GEOM, the `ng` entries of the geometric-cost-only list) of one phase.
 template <bool GEOM, int NW, int CAP, bool MUBUF, bool PROF, int HELP = 1>
 __device__ __forceinline__ void run_tasks_wave(const PmParams& p, const Lds& L, const v4i srd, int row, int col0,
-                                               int tid, int n, int ng, unsigned& evals, unsigned long long* prof_acc,
-                                               unsigned long long& prof_t, const int prof_slot0) {
+                                               int tid, int n, int ng, unsigned& evals, unsigned& answered_n,
+                                               unsigned long long* prof_acc, unsigned long long& prof_t,
+                                               const int prof_slot0) {
   const lds_f32* G = L.tapg;
-  evals += (unsigned)n;
+  evals += (unsigned)n;  // every task, answered or not (pm_get_evaluation_count); answered_n: those without taps
   const LDS_AS uint16_t* tasks = (const LDS_AS uint16_t*)L.tasks;
   const int S = p.S, S1 = p.S + 1;
   if (GEOM) {
@@ -1877,7 +1893,7 @@ __device__ __forceinline__ void run_tasks_wave(const PmParams& p, const Lds& L, 
     const int nb4 = (nb + 3) & ~3;  // whole rounds: lanes nb .. nb4 - 1 pad the batch with its last task
     PM_MARK("passA");
     // pass A, lane per task: homography of the (hypothesis, view) pair (+ geometric cost), round record
-    bool inside = false;
+    bool inside = false, answered = false;
     float Hm[9] = {};
     int c = 0, s = 0;
     if (tid < nb4) {
@@ -1890,26 +1906,24 @@ __device__ __forceinline__ void run_tasks_wave(const PmParams& p, const Lds& L, 
       const int col = col0 + c;
       compose_homography(p.refInvK, pose, row, col, h[0], h[1], h[2], h[3], Hm);
       centre_homography(Hm, row, col, p.radius);
-      inside = tid < nb && patch_inside(p, Hm);
       if (GEOM && tid < nb) L.geo[(c * 5 + i) * S1 + s] = geom_cost(p, pose, s, (float)row, (float)col, h[0]);
     }
-    unsigned long long m1;
-    const int n_inside = batch_publish<MUBUF>(p, L, tid, nb4, inside, Hm, c, s, m1);
+    task_class(p, Hm, tid < nb, tid >= nb && tid < nb4, L.colf[c * 8 + 0], L.colf[c * 8 + 1], inside, answered);
+    unsigned long long m1, m2;
+    const BatchRounds br = batch_publish<MUBUF>(p, L, tid, nb, nb4, inside, answered, Hm, c, s, m1, m2);
+    answered_n += (unsigned)batch_skipped(br);
     wave_sync<NW>();
     // pass B (ncc_rounds_wave); with a helper wave (HELP = 2, pm_sweep_pair_kernel) this wave takes every other round
     if (HELP > 1) {
       if (tid == 0) {
-        L.best[kPairNb] = nb | (n_inside << 8);
+        L.best[kPairNb] = br.nb | (br.fast << 8) | (br.rounds << 16);
         L.best[kPairLast] = base + CAP >= n ? 1 : 0;
       }
       __syncthreads();  // the batch is published: homographies, descriptors, its size
     }
     PM_PROF_MARK(prof_slot0 - 1)
     PM_MARK("passB");
-    {
-      const int rounds = (nb + 3) >> 2;
-      ncc_rounds_wave<MUBUF>(p, L, srd, G, tid, nb, n_inside, HELP > 1 ? (rounds & 1) : 0, HELP);
-    }
+    ncc_rounds_wave<MUBUF>(p, L, srd, G, tid, br, HELP > 1 ? (br.rounds & 1) : 0, HELP);
     if (HELP > 1) __syncthreads();  // the helper's sums are in
     wave_sync<NW>();
     PM_PROF_MARK(prof_slot0)
@@ -1920,7 +1934,7 @@ __device__ __forceinline__ void run_tasks_wave(const PmParams& p, const Lds& L, 
       const int c = task >> 13;
       const int i = (task >> 9) & 7;
       const int s = task & 0x1ff;
-      const lds_f32* sums = L.th + batch_position(m1, nb4, tid, ((m1 >> tid) & 1ull) != 0ull) * kSlotWords;
+      const lds_f32* sums = L.th + batch_position(m1, m2, nb4, tid) * kSlotWords;
       L.cost5[(c * 5 + i) * S1 + s] = ncc_finish(sums[0], sums[1], sums[2],
                                                  L.colf[c * 8 + 0], L.colf[c * 8 + 1], L.colf[c * 8 + 5]);
     }
@@ -2005,9 +2019,9 @@ __device__ __forceinline__ void sweep_wave_body(const PmParams* __restrict__ pp)
           __syncthreads();
           const int mail = L.best[kPairNb];
           last = L.best[kPairLast];
-          const int nb = mail & 0xff;
-          const int rounds = (nb + 3) >> 2;
-          if (nb > 0) ncc_rounds_wave<MUBUF>(p, L, srd, L.tapg, tid, nb, mail >> 8, (rounds - 1) & 1, HELP);
+          const BatchRounds br = {mail & 0xff, mail >> 16, (mail >> 8) & 0xff};
+          // (a batch of answered tasks alone has no round to run)
+          if (br.rounds > 0) ncc_rounds_wave<MUBUF>(p, L, srd, L.tapg, tid, br, (br.rounds - 1) & 1, HELP);
           __syncthreads();
         } while (!last);
       }
@@ -2038,6 +2052,7 @@ __device__ __forceinline__ void sweep_wave_body(const PmParams* __restrict__ pp)
   unsigned long long prof_acc[kProfSlots] = {};
   unsigned long long prof_t = PROF ? __builtin_readcyclecounter() : 0ull;
   unsigned evals = 0;  // NCC evaluations of this wave (< 2^32: RH * C * (4 M + S) per sweep)
+  unsigned answered_n = 0;  // those of them that pass B never ran (batch_skipped)
   // ring slots of the tile rows row - radius, row, row + radius (advance by one per row, modulo the window)
   int slot_top = p.radius + 1 == win ? 0 : p.radius + 1, slot_c = 0, slot_new = p.radius;
   const int step0 = 1 << (31 - __builtin_clz(S));  // largest power of two <= S (CDF search)
@@ -2150,7 +2165,7 @@ __device__ __forceinline__ void sweep_wave_body(const PmParams* __restrict__ pp)
     PM_MARK("P4");
     // ---- P4: NCC of hypotheses 1..4 against the drawn views (:1157-1172) -----
     if (HELP > 1 || !(PM_ABLATE(p) & 1))
-      run_tasks_wave<GEOM, NW, CAP, MUBUF, PROF, HELP>(p, L, srd, row, col0, tid, n4, ng, evals, prof_acc, prof_t, kProfP4B);
+      run_tasks_wave<GEOM, NW, CAP, MUBUF, PROF, HELP>(p, L, srd, row, col0, tid, n4, ng, evals, answered_n, prof_acc, prof_t, kProfP4B);
 
     PM_PROF_MARK(kProfP4F)
     PM_MARK("P5a");
@@ -2204,7 +2219,7 @@ __device__ __forceinline__ void sweep_wave_body(const PmParams* __restrict__ pp)
     PM_MARK("P6");
     // ---- P6: NCC of the winner against the remaining views (:1188-1197) ------
     if (HELP > 1 || !(PM_ABLATE(p) & 1))
-      run_tasks_wave<false, NW, CAP, MUBUF, PROF, HELP>(p, L, srd, row, col0, tid, n1, 0, evals, prof_acc, prof_t, kProfP6B);
+      run_tasks_wave<false, NW, CAP, MUBUF, PROF, HELP>(p, L, srd, row, col0, tid, n1, 0, evals, answered_n, prof_acc, prof_t, kProfP6B);
     PM_PROF_MARK(kProfP6F)
     PM_MARK("P7");
 
@@ -2230,6 +2245,7 @@ __device__ __forceinline__ void sweep_wave_body(const PmParams* __restrict__ pp)
   }
 
   if (tid == 0 && p.evals) atomicAdd(p.evals, (unsigned long long)evals);
+  if (tid == 0 && p.answered) atomicAdd(p.answered, (unsigned long long)answered_n);
   if (PROF) {
     PM_PROF_MARK(kProfP8)
     if (tid == 0 && p.prof) {
@@ -2292,6 +2308,7 @@ __global__ void __launch_bounds__(64 * kQuadWaves, kQuadOcc) pm_initial_cost_wav
   int slot_c = row0 % win, slot_top = (row0 - p.radius) % win, slot_new = (row0 + p.radius) % win;
   if (slot_top < 0) slot_top += win;
   const int n = ncols * S;
+  unsigned answered_n = 0;  // tasks of this wave that pass B never ran (pm_get_answered_count, second counter)
   for (int row = row0; row < row1; ++row) {
     int tid = tid0;
     launder_vgpr(tid);  // (as in the sweep: nothing derived from the lane id lives across the NCC rounds)
@@ -2304,8 +2321,8 @@ __global__ void __launch_bounds__(64 * kQuadWaves, kQuadOcc) pm_initial_cost_wav
       const int nb = min(CAP, n - base);
       const int nb4 = (nb + 3) & ~3;  // whole rounds: lanes nb .. nb4 - 1 pad the batch with its last task
       // pass A, lane per (column, view): the homography of the pixel's initial plane, round record
-      bool inside = false;
-      float Hm[9] = {};
+      bool inside = false, answered = false;
+      float Hm[9] = {}, ref_sum = 0.0f, ref_sqsum = 0.0f;
       int c = 0, sv = 0;
       if (tid < nb4) {
         const int t = base + min(tid, nb - 1);
@@ -2315,18 +2332,22 @@ __global__ void __launch_bounds__(64 * kQuadWaves, kQuadOcc) pm_initial_cost_wav
         const float* rec = p.rec + (size_t)(row * p.W + col) * p.rec_stride;
         compose_homography(p.refInvK, L.poses + sv * L.pstride, row, col, rec[0], rec[1], rec[2], rec[3], Hm);
         centre_homography(Hm, row, col, p.radius);
-        inside = tid < nb && patch_inside(p, Hm);
+        const int pix = row * p.W + col;
+        ref_sum = p.ref_sum[pix];
+        ref_sqsum = p.ref_sqsum[pix];
       }
-      unsigned long long m1;
-      const int n_inside = batch_publish<MUBUF>(p, L, tid, nb4, inside, Hm, c, sv, m1);
+      task_class(p, Hm, tid < nb, tid >= nb && tid < nb4, ref_sum, ref_sqsum, inside, answered);
+      unsigned long long m1, m2;
+      const BatchRounds br = batch_publish<MUBUF>(p, L, tid, nb, nb4, inside, answered, Hm, c, sv, m1, m2);
+      answered_n += (unsigned)batch_skipped(br);
       wave_sync<NW>();
-      ncc_rounds_wave<MUBUF>(p, L, srd, L.tapg, tid, nb, n_inside, 0, 1);
+      ncc_rounds_wave<MUBUF>(p, L, srd, L.tapg, tid, br, 0, 1);
       wave_sync<NW>();
       if (tid < nb) {
         const int t = base + tid;
         const int c = t / S, sv = t - c * S;
         const int pix = row * p.W + col0 + c;
-        const lds_f32* sums = L.th + batch_position(m1, nb4, tid, ((m1 >> tid) & 1ull) != 0ull) * kSlotWords;
+        const lds_f32* sums = L.th + batch_position(m1, m2, nb4, tid) * kSlotWords;
         p.rec[(size_t)pix * p.rec_stride + 4 + sv] =
             ncc_finish(sums[0], sums[1], sums[2], p.ref_sum[pix], p.ref_sqsum[pix], L.colf[c * 8 + 5]);
       }
@@ -2336,6 +2357,7 @@ __global__ void __launch_bounds__(64 * kQuadWaves, kQuadOcc) pm_initial_cost_wav
     slot_c = slot_c + 1 == win ? 0 : slot_c + 1;
     slot_new = slot_new + 1 == win ? 0 : slot_new + 1;
   }
+  if (tid0 == 0 && p.answered) atomicAdd(p.answered + 1, (unsigned long long)answered_n);
 }
 
 // Four waves per workgroup, each with its own column group, sharing one LDS copy of the read-only per-problem

@@ -371,6 +371,13 @@ class PatchMatch:
         _check(lib().pm_get_evaluation_count(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def GetAnsweredCount(self):
+        """(sweep launches, ComputeInitialCost): evaluations of the last run that the 11 x 11 kernels answered without
+        taps -- patch wholly beside its source image, or flat reference patch. GetEvaluationCount includes them."""
+        a, b = C.c_ulonglong(), C.c_ulonglong()
+        _check(lib().pm_get_answered_count(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def EnablePhaseProfile(self, enable=True):
         _check(lib().pm_enable_phase_profile(self._h, 1 if enable else 0))
 

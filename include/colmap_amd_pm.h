@@ -170,6 +170,10 @@ int pm_get_sweep_kernel_name(pm_handle* h, const char** name);
  * ComputeInitialCost (W * H * S). With geom_consistency the sweep count also includes the
  * geometric-cost-only entries when the two-wave kernel runs. bench.py turns it into taps/s. */
 int pm_get_evaluation_count(pm_handle* h, unsigned long long* sweep_evals, unsigned long long* initial_evals);
+/* Of those evaluations, the ones the 11 x 11 wave kernels answered without running a tap (the last run; 0 for the
+ * generic kernels): the patch lies wholly beside its source image, so its three window sums are +0, or the reference
+ * patch is flat, so the cost is 2 whatever the sums. pm_get_evaluation_count keeps counting them. */
+int pm_get_answered_count(pm_handle* h, unsigned long long* sweep_answered, unsigned long long* initial_answered);
 /* Device pointers of the result maps in API layout (valid after pm_synchronize;
  * for consumers that stay on the GPU, e.g. the geometric pass). */
 int pm_get_device_maps(pm_handle* h, const float** depth, const float** normal);

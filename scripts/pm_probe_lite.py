@@ -102,6 +102,15 @@ def run(a):
               f"{mpix / tr:.3f} Mpix/s (run), {mpix / (tr + tc):.3f} incl. create; sweep launch avg {ms / max(n, 1):.2f} ms x {n}; "
               f"NCC evaluations per pixel per sweep {sum(e[0] for e in ev) / (batch * w * h * max(n, 1)):.2f}", flush=True)
         print("  per launch ms: " + " ".join(f"{v:.0f}" for v in pms[0].GetSweepTimes()), flush=True)
+        answered = None
+        if hasattr(mvs.lib(), "pm_get_answered_count"):   # (PM_PROBE_LIB may be a build from before the counter)
+            an = [pm.GetAnsweredCount() for pm in pms]
+            answered = {"sweep_evaluations": sum(e[0] for e in ev), "sweep_answered": sum(x[0] for x in an),
+                        "initial_evaluations": sum(e[1] for e in ev), "initial_answered": sum(x[1] for x in an)}
+            answered["sweep_share"] = answered["sweep_answered"] / max(answered["sweep_evaluations"], 1)
+            answered["initial_share"] = answered["initial_answered"] / max(answered["initial_evaluations"], 1)
+            print(f"  answered without taps: sweeps {answered['sweep_share']:.4f} of the evaluations, "
+                  f"initial cost {answered['initial_share']:.4f}", flush=True)
         if a.profile:
             import json
             tot = {}
@@ -114,6 +123,8 @@ def run(a):
                    "sweep_launch_ms_avg": ms / max(n, 1), "waves_reported": waves, "cycles_total": cyc,
                    "cycles_per_wave_row": cyc / max(waves, 1) / (h if True else w),
                    "share": {k: round(v / cyc, 4) for k, v in tot.items()}, "cycles": tot}
+            if answered is not None:
+                out["answered"] = answered
             print("PHASE_PROFILE " + json.dumps(out), flush=True)
             if a.profile_out:
                 os.makedirs(os.path.dirname(a.profile_out), exist_ok=True)
