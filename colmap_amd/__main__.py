@@ -8,6 +8,10 @@ COMMANDS = {
     "bundle_adjuster": ("colmap_amd.bundle_adjuster", "global bundle adjustment of a sparse model (exe/sfm.cc:175-206)"),
     "point_filtering": ("colmap_amd.point_filtering", "filter outlier observations and points of a sparse model (exe/sfm.cc:556-587)"),
     "image_undistorter": ("colmap_amd.image_undistorter", "undistort images into a dense workspace (exe/image.cc:325-430)"),
+    "image_undistorter_standalone": ("colmap_amd.image_undistorter_standalone",
+                                     "undistort images whose cameras come from a text list (exe/image.cc:427-523)"),
+    "image_rectifier": ("colmap_amd.image_rectifier", "rectify and undistort stereo pairs, write Q (exe/image.cc:211-251)"),
+    "color_extractor": ("colmap_amd.color_extractor", "colour the 3D points of a sparse model from its images (exe/sfm.cc:208-228)"),
 }
 
 
@@ -16,7 +20,7 @@ def main(argv=None) -> int:
     if not argv or argv[0] in ("-h", "--help", "help"):
         print("usage: python -m colmap_amd <command> [options]\n\ncommands:")
         for name, (_, what) in COMMANDS.items():
-            print(f"  {name:20s} {what}")
+            print(f"  {name:28s} {what}")
         return 0
     if argv[0] not in COMMANDS:
         print(f"E Command `{argv[0]}` not recognized. To list the available commands, run `python -m colmap_amd help`.",

@@ -1,6 +1,6 @@
 // undistort.hip -- image undistortion on gfx950 behind include/colmap_amd_undistort.h.
 //
-// Three kernels, all geometry in double:
+// Four kernels, all geometry in double:
 //   undistort_warp_kernel<INTERP, C>   one target pixel = target pinhole CamFromImg -> source ImgFromCam -> sample
 //                                      (reference image/warp.cc:91-144, sensor/bitmap.cc InterpolateBilinear /
 //                                      InterpolateNearestNeighbor). The source model is a kernel argument, uniform over
@@ -9,10 +9,13 @@
 //                                      stores them as whole dwords (1 for grey, 3 for RGB) into a device image whose row
 //                                      pitch is padded to whole groups. Source texels are read through the caches:
 //                                      neighbouring lanes read neighbouring texels, nothing is staged in LDS.
+//   undistort_rectify_kernel<INTERP, C> the same work shape with a homography in front of the target camera: one target
+//                                      pixel = Hinv (x + 1/2, y + 1/2, 1) -> target pinhole CamFromImg -> source
+//                                      ImgFromCam -> sample (image/warp.cc:196-250), for stereo rectification
 //   undistort_points_kernel            one lane per observation (image/undistortion.cc:334-381)
 //   undistort_resize_kernel<C>         the triangle filter defined at the kernel (indirect path of
 //                                      WarpImageBetweenCameras, and spherical images with max_image_size)
-// undistort_camera / undistort_cam_from_img are host functions over the same camera_projection.h.
+// undistort_camera / undistort_cam_from_img / undistort_rectify_cameras are host functions over the same camera_projection.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -161,6 +164,69 @@ undistort_warp_kernel(CamArgs src, double tfx, double tfy, double tcx, double tc
 #define UD_CASE(M)                                                                                        \
   case ud::M:                                                                                             \
     warp_group<ud::M, INTERP, C>(src, tfx, tfy, tcx, tcy, in, in_pitch, out, out_pitch_dwords, W, H); \
+    break;
+  switch (src.model) {  // uniform over the launch
+    UD_CASE(SIMPLE_PINHOLE) UD_CASE(PINHOLE) UD_CASE(SIMPLE_RADIAL) UD_CASE(RADIAL) UD_CASE(OPENCV)
+    UD_CASE(OPENCV_FISHEYE) UD_CASE(FULL_OPENCV) UD_CASE(FOV) UD_CASE(SIMPLE_RADIAL_FISHEYE) UD_CASE(RADIAL_FISHEYE)
+    UD_CASE(THIN_PRISM_FISHEYE) UD_CASE(RAD_TAN_THIN_PRISM_FISHEYE) UD_CASE(SIMPLE_DIVISION) UD_CASE(DIVISION)
+    UD_CASE(SIMPLE_FISHEYE) UD_CASE(FISHEYE) UD_CASE(EUCM)
+    default: break;  // the host never launches a spherical source
+  }
+#undef UD_CASE
+}
+
+// ---- stereo rectification (undistort_rectify_kernel, WarpImageWithHomographyBetweenCameras image/warp.cc:196-250) ----
+struct Homography {  // row-major 3x3, the inverse of H1 / H2 of RectifyStereoCameras: target pixel -> unrectified target pixel
+  double h[9];
+};
+
+// warp_group with a homography in front of the target camera (image/warp.cc:214-245): w = Hinv (x + 1/2, y + 1/2, 1); a
+// pixel with w.z == 0 is 0; otherwise the target pinhole CamFromImg of w.hnormalized(), the source ImgFromCam, the sample.
+template <int MODEL, int INTERP, int C>
+__device__ __forceinline__ void rectify_group(const CamArgs& src, const Homography& Hinv, double tfx, double tfy,
+                                              double tcx, double tcy, const uint8_t* __restrict__ in, int in_pitch,
+                                              uint32_t* __restrict__ out, int out_pitch_dwords, int W, int H) {
+  const int gx = (blockIdx.x * blockDim.x + threadIdx.x) * kPixelsPerLane;
+  const int y = blockIdx.y * blockDim.y + threadIdx.y;
+  if (gx >= W || y >= H) return;
+  const double py = (double)y + 0.5;
+  unsigned px[kPixelsPerLane * C];
+#pragma unroll
+  for (int k = 0; k < kPixelsPerLane; ++k) {
+    unsigned* o = px + k * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = 0u;
+    const int x = gx + k;
+    if (x >= W) continue;
+    const double pxc = (double)x + 0.5;
+    const double wx = Hinv.h[0] * pxc + Hinv.h[1] * py + Hinv.h[2];
+    const double wy = Hinv.h[3] * pxc + Hinv.h[4] * py + Hinv.h[5];
+    const double wz = Hinv.h[6] * pxc + Hinv.h[7] * py + Hinv.h[8];
+    if (wz == 0.0) continue;
+    const double u = (wx / wz - tcx) / tfx;  // PinholeCameraModel::CamFromImg of the target
+    const double v = (wy / wz - tcy) / tfy;
+    double sx, sy;
+    if (!ud::img_from_normalized(MODEL, src.p, u, v, &sx, &sy)) continue;
+    unsigned s[C];
+    if (sample<INTERP, C>(in, in_pitch, src.width, src.height, sx - 0.5, sy - 0.5, s)) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) o[c] = s[c];
+    }
+  }
+  uint32_t* dst = out + (size_t)y * out_pitch_dwords + (size_t)(gx / kPixelsPerLane) * C;
+#pragma unroll
+  for (int d = 0; d < C; ++d)
+    dst[d] = px[4 * d] | (px[4 * d + 1] << 8) | (px[4 * d + 2] << 16) | (px[4 * d + 3] << 24);
+}
+
+template <int INTERP, int C>
+__global__ void __launch_bounds__(256)
+undistort_rectify_kernel(CamArgs src, Homography Hinv, double tfx, double tfy, double tcx, double tcy,
+                         const uint8_t* __restrict__ in, int in_pitch, uint32_t* __restrict__ out, int out_pitch_dwords,
+                         int W, int H) {
+#define UD_CASE(M)                                                                                             \
+  case ud::M:                                                                                                  \
+    rectify_group<ud::M, INTERP, C>(src, Hinv, tfx, tfy, tcx, tcy, in, in_pitch, out, out_pitch_dwords, W, H); \
     break;
   switch (src.model) {  // uniform over the launch
     UD_CASE(SIMPLE_PINHOLE) UD_CASE(PINHOLE) UD_CASE(SIMPLE_RADIAL) UD_CASE(RADIAL) UD_CASE(OPENCV)
@@ -331,6 +397,27 @@ void launch_warp(const undistort_cam& source, const undistort_cam& target, int i
   UD_HIP(hipGetLastError());
 }
 
+void launch_rectify(const undistort_cam& source, const undistort_cam& target, const Homography& Hinv, int interpolation,
+                    int channels, const uint8_t* d_in, uint32_t* d_out) {
+  UD_CHECK(target.model_id == ud::PINHOLE, "the warp target is a PINHOLE camera");
+  const CamArgs src = to_args(source);
+  const int W = target.width, H = target.height;
+  const int in_pitch = source.width * channels, out_pitch = padded_pitch(W, channels) / 4;
+  const dim3 block(64, 4);
+  const dim3 grid = image_grid(W, H, block);
+  const double fx = target.params[0], fy = target.params[1], cx = target.params[2], cy = target.params[3];
+#define UD_LAUNCH(I, C)                                                                                             \
+  hipLaunchKernelGGL((undistort_rectify_kernel<I, C>), grid, block, 0, 0, src, Hinv, fx, fy, cx, cy, d_in, in_pitch, \
+                     d_out, out_pitch, W, H)
+  if (interpolation == UNDISTORT_BILINEAR) {
+    if (channels == 1) UD_LAUNCH(UNDISTORT_BILINEAR, 1); else UD_LAUNCH(UNDISTORT_BILINEAR, 3);
+  } else {
+    if (channels == 1) UD_LAUNCH(UNDISTORT_NEAREST, 1); else UD_LAUNCH(UNDISTORT_NEAREST, 3);
+  }
+#undef UD_LAUNCH
+  UD_HIP(hipGetLastError());
+}
+
 void launch_resize(const uint8_t* d_src, int src_pitch, int SW, int SH, int channels, uint32_t* d_out, int W, int H) {
   const dim3 block(64, 4);
   const dim3 grid = image_grid(W, H, block);
@@ -488,6 +575,143 @@ bool should_warp_directly(const undistort_cam& s, const undistort_cam& t, double
   return std::min(scale_x, scale_y) >= direct_warp_min_scale;
 }
 
+// ---- RectifyStereoCameras (image/undistortion.cc:384-445), Eigen's operations restated on row-major 3x3 arrays ----
+void mat3_mul(const double* a, const double* b, double* c) {
+  double r[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) r[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+  std::memcpy(c, r, sizeof(r));
+}
+
+void mat3_vec(const double* a, const double* v, double* out) {
+  double r[3];
+  for (int i = 0; i < 3; ++i) r[i] = a[3 * i] * v[0] + a[3 * i + 1] * v[1] + a[3 * i + 2] * v[2];
+  std::memcpy(out, r, sizeof(r));
+}
+
+// Eigen::AngleAxisd::toRotationMatrix
+void rotation_from_angle_axis(double angle, const double* axis, double* m) {
+  const double s = std::sin(angle), c = std::cos(angle);
+  const double sa[3] = {s * axis[0], s * axis[1], s * axis[2]};
+  const double ca[3] = {(1.0 - c) * axis[0], (1.0 - c) * axis[1], (1.0 - c) * axis[2]};
+  double tmp = ca[0] * axis[1];
+  m[1] = tmp - sa[2];
+  m[3] = tmp + sa[2];
+  tmp = ca[0] * axis[2];
+  m[2] = tmp + sa[1];
+  m[6] = tmp - sa[1];
+  tmp = ca[1] * axis[2];
+  m[5] = tmp - sa[0];
+  m[7] = tmp + sa[0];
+  m[0] = ca[0] * axis[0] + c;
+  m[4] = ca[1] * axis[1] + c;
+  m[8] = ca[2] * axis[2] + c;
+}
+
+// Eigen::AngleAxisd(Matrix3d): through the quaternion (Eigen/src/Geometry/Quaternion.h quaternionbase_assign_impl,
+// AngleAxis.h operator=(QuaternionBase)); angle in [0, pi], axis (1, 0, 0) for the identity
+void angle_axis_from_rotation(const double* m, double* angle, double* axis) {
+  double q[4];  // x, y, z, w
+  double t = m[0] + m[4] + m[8];
+  if (t > 0.0) {
+    t = std::sqrt(t + 1.0);
+    q[3] = 0.5 * t;
+    t = 0.5 / t;
+    q[0] = (m[7] - m[5]) * t;
+    q[1] = (m[2] - m[6]) * t;
+    q[2] = (m[3] - m[1]) * t;
+  } else {
+    int i = 0;
+    if (m[4] > m[0]) i = 1;
+    if (m[8] > m[4 * i]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    t = std::sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
+    q[i] = 0.5 * t;
+    t = 0.5 / t;
+    q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
+    q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
+    q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
+  }
+  double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+  if (n != 0.0) {
+    *angle = 2.0 * std::atan2(n, std::fabs(q[3]));
+    if (q[3] < 0.0) n = -n;
+    axis[0] = q[0] / n;
+    axis[1] = q[1] / n;
+    axis[2] = q[2] / n;
+  } else {
+    *angle = 0.0;
+    axis[0] = 1.0;
+    axis[1] = axis[2] = 0.0;
+  }
+}
+
+// the inverse of a 3x3 matrix by cofactors; false when the determinant is 0 or not finite
+bool mat3_inverse(const double* a, double* inv) {
+  const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[5] * a[6] - a[3] * a[8], c02 = a[3] * a[7] - a[4] * a[6];
+  const double det = a[0] * c00 + a[1] * c01 + a[2] * c02;
+  if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return false;
+  const double r[9] = {c00 / det, (a[2] * a[7] - a[1] * a[8]) / det, (a[1] * a[5] - a[2] * a[4]) / det,
+                       c01 / det, (a[0] * a[8] - a[2] * a[6]) / det, (a[2] * a[3] - a[0] * a[5]) / det,
+                       c02 / det, (a[1] * a[6] - a[0] * a[7]) / det, (a[0] * a[4] - a[1] * a[3]) / det};
+  std::memcpy(inv, r, sizeof(r));
+  return true;
+}
+
+void rectify_cameras_impl(const undistort_cam& cam1, const undistort_cam& cam2, const double* R, const double* t_in,
+                          double* H1, double* H2, double* Q) {
+  check_camera(cam1);
+  check_camera(cam2);
+  UD_CHECK(cam1.model_id == ud::SIMPLE_PINHOLE || cam1.model_id == ud::PINHOLE,
+           "Check failed: camera1.model_id == SimplePinholeCameraModel::model_id || camera1.model_id == "
+           "PinholeCameraModel::model_id");
+  UD_CHECK(cam2.model_id == ud::SIMPLE_PINHOLE || cam2.model_id == ud::PINHOLE,
+           "Check failed: camera2.model_id == SimplePinholeCameraModel::model_id || camera2.model_id == "
+           "PinholeCameraModel::model_id");
+  // the average rotation between the first and the second camera (:395-400)
+  double angle, axis[3], R1[9], R2[9], t[3];
+  angle_axis_from_rotation(R, &angle, axis);
+  angle *= -0.5;
+  rotation_from_angle_axis(angle, axis, R2);
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) R1[3 * i + j] = R2[3 * j + i];
+  // the translation, such that it coincides with the x axis (:402-419)
+  mat3_vec(R2, t_in, t);
+  double x_unit[3] = {1.0, 0.0, 0.0};
+  if (t[0] * x_unit[0] + t[1] * x_unit[1] + t[2] * x_unit[2] < 0.0) x_unit[0] = -1.0;
+  const double rot_axis[3] = {t[1] * x_unit[2] - t[2] * x_unit[1], t[2] * x_unit[0] - t[0] * x_unit[2],
+                              t[0] * x_unit[1] - t[1] * x_unit[0]};
+  const double rot_norm = std::sqrt(rot_axis[0] * rot_axis[0] + rot_axis[1] * rot_axis[1] + rot_axis[2] * rot_axis[2]);
+  double R_x[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  if (!(rot_norm < std::numeric_limits<double>::epsilon())) {
+    const double t_norm = std::sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+    const double x_norm = std::sqrt(x_unit[0] * x_unit[0] + x_unit[1] * x_unit[1] + x_unit[2] * x_unit[2]);
+    const double a = std::acos(std::fabs(t[0] * x_unit[0] + t[1] * x_unit[1] + t[2] * x_unit[2]) / (t_norm * x_norm));
+    const double n[3] = {rot_axis[0] / rot_norm, rot_axis[1] / rot_norm, rot_axis[2] / rot_norm};
+    rotation_from_angle_axis(a, n, R_x);
+  }
+  mat3_mul(R_x, R1, R1);
+  mat3_mul(R_x, R2, R2);
+  mat3_vec(R_x, t, t);
+  // the intrinsic calibration matrix (:426-431)
+  const ud::Intrinsics k1 = ud::intrinsics(cam1.model_id, cam1.params), k2 = ud::intrinsics(cam2.model_id, cam2.params);
+  const double f = std::min((k1.f1 + k1.f2) / 2.0, (k2.f1 + k2.f2) / 2.0);
+  const double K[9] = {f, 0, k1.c1, 0, f, (k1.c2 + k2.c2) / 2.0, 0, 0, 1};
+  double K1[9] = {k1.f1, 0, k1.c1, 0, k1.f2, k1.c2, 0, 0, 1}, K2[9] = {k2.f1, 0, k2.c1, 0, k2.f2, k2.c2, 0, 0, 1};
+  UD_CHECK(mat3_inverse(K1, K1) && mat3_inverse(K2, K2), "a calibration matrix is singular");
+  mat3_mul(K, R1, H1);
+  mat3_mul(H1, K1, H1);
+  mat3_mul(K, R2, H2);
+  mat3_mul(H2, K2, H2);
+  // [x, y, disparity, 1] * Q = [X, Y, Z, 1] * w (:437-444), entries as the reference writes them
+  for (int i = 0; i < 16; ++i) Q[i] = (i % 5 == 0) ? 1.0 : 0.0;
+  Q[12] = -K[5];
+  Q[13] = -K[2];
+  Q[14] = K[0];
+  Q[11] = -1.0 / t[0];
+  Q[15] = 0.0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -593,6 +817,134 @@ UNDISTORT_API int undistort_images(const undistort_options* options, int32_t num
     }
     g_kernel_ms = kernel_ms;
     g_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  });
+}
+
+UNDISTORT_API int undistort_rectify_cameras(const undistort_cam* camera1, const undistort_cam* camera2, const double* R,
+                                            const double* t, double* H1, double* H2, double* Q) {
+  return Guard([&] {
+    UD_CHECK(camera1 && camera2 && R && t && H1 && H2 && Q, "null argument");
+    rectify_cameras_impl(*camera1, *camera2, R, t, H1, H2, Q);
+  });
+}
+
+UNDISTORT_API int undistort_rectify_images(const undistort_options* options, int32_t num_pairs, undistort_stereo_pair* pairs,
+                                           int32_t gpu_index) {
+  return Guard([&] {
+    UD_CHECK(options && (num_pairs == 0 || pairs) && num_pairs >= 0, "null argument");
+    check_options(*options);
+    UD_CHECK(options->interpolation == UNDISTORT_BILINEAR || options->interpolation == UNDISTORT_NEAREST,
+             "Invalid warp image interpolation mode: " + std::to_string(options->interpolation));
+    // everything the caller can get wrong is checked before the first byte moves
+    struct PairPlan {
+      undistort_cam target;
+      Homography Hinv[2];
+    };
+    std::vector<PairPlan> plans(num_pairs);
+    for (int i = 0; i < num_pairs; ++i) {
+      undistort_stereo_pair& pr = pairs[i];
+      undistort_image* im[2] = {&pr.image1, &pr.image2};
+      const std::string who = "pair " + std::to_string(i);
+      for (int s = 0; s < 2; ++s) {
+        check_camera(im[s]->camera);
+        UD_CHECK(ud::is_perspective(im[s]->camera.model_id), who + ": Check failed: camera.IsPerspective()");
+        UD_CHECK(im[s]->data && im[s]->out, who + ": null pixel buffer");
+        UD_CHECK(im[s]->channels == 1 || im[s]->channels == 3, who + ": channels must be 1 (grey) or 3 (RGB)");
+      }
+      undistort_camera_impl(*options, pr.image1.camera, &plans[i].target);  // camera 1 only (:462, :475-476)
+      double H1[9], H2[9];
+      rectify_cameras_impl(plans[i].target, plans[i].target, pr.R, pr.t, H1, H2, pr.Q);
+      UD_CHECK(mat3_inverse(H1, plans[i].Hinv[0].h) && mat3_inverse(H2, plans[i].Hinv[1].h),
+               who + ": a rectifying homography is singular");
+      for (int s = 0; s < 2; ++s) {
+        const size_t need = (size_t)plans[i].target.width * plans[i].target.height * im[s]->channels;
+        UD_CHECK(im[s]->out_capacity >= need, who + ": output buffer of " + std::to_string(im[s]->out_capacity) +
+                                                  " bytes, " + std::to_string(need) + " needed");
+      }
+    }
+    bind_device(gpu_index);
+    const auto t0 = std::chrono::steady_clock::now();
+    DeviceBuffer<uint8_t> d_in;
+    DeviceBuffer<uint32_t> d_out, d_mid;
+    Timer ev;
+    double kernel_ms = 0.0;
+    for (int i = 0; i < num_pairs; ++i) {
+      undistort_image* im[2] = {&pairs[i].image1, &pairs[i].image2};
+      const undistort_cam& tgt = plans[i].target;
+      for (int s = 0; s < 2; ++s) {
+        const undistort_cam& src = im[s]->camera;
+        const int C = im[s]->channels;
+        const size_t in_bytes = (size_t)src.width * src.height * C;
+        im[s]->out_camera = tgt;
+        d_in.reserve(in_bytes);
+        d_out.reserve((size_t)padded_pitch(tgt.width, C) / 4 * tgt.height);
+        UD_HIP(hipMemcpyAsync(d_in.p, im[s]->data, in_bytes, hipMemcpyHostToDevice, 0));
+        UD_HIP(hipEventRecord(ev.a, 0));
+        if (should_warp_directly(src, tgt, options->direct_warp_min_scale)) {
+          launch_rectify(src, tgt, plans[i].Hinv[s], options->interpolation, C, d_in.p, d_out.p);
+        } else {
+          // The consistent indirect path (see the header): the target camera rescaled to the source's size
+          // (image/warp.cc:103-106), the homography conjugated with that pixel scaling S = diag(sx, sy, 1) -- S Hinv S^-1,
+          // which in front of the rescaled camera is Hinv diag(1/sx, 1/sy, 1) in front of the target camera --, the warp
+          // at source size, then the shrink.
+          undistort_cam mid = tgt;
+          rescale_camera(&mid, src.width, src.height);
+          const double sx = (double)mid.width / (double)tgt.width, sy = (double)mid.height / (double)tgt.height;
+          Homography Hs = plans[i].Hinv[s];
+          Hs.h[1] = Hs.h[1] * sx / sy;
+          Hs.h[2] = Hs.h[2] * sx;
+          Hs.h[3] = Hs.h[3] * sy / sx;
+          Hs.h[5] = Hs.h[5] * sy;
+          Hs.h[6] = Hs.h[6] / sx;
+          Hs.h[7] = Hs.h[7] / sy;
+          d_mid.reserve((size_t)padded_pitch(mid.width, C) / 4 * mid.height);
+          launch_rectify(src, mid, Hs, options->interpolation, C, d_in.p, d_mid.p);
+          launch_resize((const uint8_t*)d_mid.p, padded_pitch(mid.width, C), mid.width, mid.height, C, d_out.p, tgt.width,
+                        tgt.height);
+        }
+        UD_HIP(hipEventRecord(ev.b, 0));
+        download(im[s]->out, d_out.p, tgt.width, tgt.height, C);
+        UD_HIP(hipEventSynchronize(ev.b));
+        float ms = 0.0f;
+        UD_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+        kernel_ms += ms;
+      }
+    }
+    g_kernel_ms = kernel_ms;
+    g_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  });
+}
+
+UNDISTORT_API int undistort_warp_homography(const undistort_options* options, const double* Hinv,
+                                            const undistort_cam* target_camera, undistort_image* image, int32_t gpu_index) {
+  return Guard([&] {
+    UD_CHECK(options && Hinv && target_camera && image, "null argument");
+    UD_CHECK(options->interpolation == UNDISTORT_BILINEAR || options->interpolation == UNDISTORT_NEAREST,
+             "Invalid warp image interpolation mode: " + std::to_string(options->interpolation));
+    check_camera(image->camera);
+    check_camera(*target_camera);
+    UD_CHECK(ud::is_perspective(image->camera.model_id), "Check failed: camera.IsPerspective()");
+    UD_CHECK(target_camera->model_id == ud::PINHOLE, "the warp target is a PINHOLE camera");
+    UD_CHECK(image->data && image->out, "null pixel buffer");
+    UD_CHECK(image->channels == 1 || image->channels == 3, "channels must be 1 (grey) or 3 (RGB)");
+    const undistort_cam& src = image->camera;
+    const undistort_cam& tgt = *target_camera;
+    const int C = image->channels;
+    const size_t need = (size_t)tgt.width * tgt.height * C;
+    UD_CHECK(image->out_capacity >= need, "output buffer of " + std::to_string(image->out_capacity) + " bytes, " +
+                                              std::to_string(need) + " needed");
+    bind_device(gpu_index);
+    Homography H;
+    for (int i = 0; i < 9; ++i) H.h[i] = Hinv[i];
+    DeviceBuffer<uint8_t> d_in;
+    DeviceBuffer<uint32_t> d_out;
+    const size_t in_bytes = (size_t)src.width * src.height * C;
+    d_in.reserve(in_bytes);
+    d_out.reserve((size_t)padded_pitch(tgt.width, C) / 4 * tgt.height);
+    UD_HIP(hipMemcpyAsync(d_in.p, image->data, in_bytes, hipMemcpyHostToDevice, 0));
+    launch_rectify(src, tgt, H, options->interpolation, C, d_in.p, d_out.p);
+    download(image->out, d_out.p, tgt.width, tgt.height, C);
+    image->out_camera = tgt;
   });
 }
 

@@ -1,5 +1,6 @@
 """pycolmap-style pipeline functions on the MI355X paths: `from colmap_amd.pipeline import
-patch_match_stereo, stereo_fusion, bundle_adjustment, filter_points, undistort_images`."""
+patch_match_stereo, stereo_fusion, bundle_adjustment, filter_points, undistort_images, rectify_images,
+undistort_images_standalone, extract_colors`."""
 # ---------------------------------------------------------------------------------------------
 # pycolmap-style pipeline functions (reference pycolmap/pipeline/mvs.cc:119-127,182-193,
 # pycolmap/pipeline/sfm.cc:153-161,258-263): same names, argument order and defaults. Imports are
@@ -82,3 +83,48 @@ def undistort_images(output_path, input_path, image_path, image_names=None, outp
                                          str(image_path), str(output_path))
     ctl.Run()
     return ctl
+
+
+def rectify_images(output_path, input_path, image_path, stereo_pairs, undistort_options=None, gpu_index=0):
+    """`colmap image_rectifier` (exe/image.cc:211-251): rectifies and undistorts the stereo pairs -- (name1, name2) image
+    names of the sparse model at input_path -- into `<output_path>/<name1>-<name2>/` with `Q.txt` (needs an MI355X)."""
+    from . import undistortion, workspace
+    model = workspace.read_sparse_model(str(input_path))
+    by_name = {img.name: iid for iid, img in model.images.items()}
+    pairs = []
+    for name1, name2 in stereo_pairs:
+        if name1 not in by_name or name2 not in by_name:
+            raise ValueError(f"image {name1 if name1 not in by_name else name2} does not exist in the reconstruction")
+        pairs.append((by_name[name1], by_name[name2]))
+    ctl = undistortion.StereoImageRectifier(undistortion.StereoImageRectifierOptions(stereo_pairs=pairs, gpu_index=gpu_index),
+                                            undistort_options or undistortion.UndistortCameraOptions(), model,
+                                            str(image_path), str(output_path))
+    ctl.Run()
+    return ctl
+
+
+def undistort_images_standalone(output_path, image_path, image_names_and_cameras, copy_policy="copy",
+                                undistort_options=None, gpu_index=0):
+    """`colmap image_undistorter_standalone` (exe/image.cc:427-523): undistorts (image name, camera) entries with no
+    model on disk (needs an MI355X)."""
+    from . import undistortion
+    opts = undistortion.StandaloneImageUndistorterOptions(image_names_and_cameras=list(image_names_and_cameras),
+                                                          copy_type=str(copy_policy).lower().replace("_", "-"),
+                                                          gpu_index=gpu_index)
+    ctl = undistortion.StandaloneImageUndistorter(opts, undistort_options or undistortion.UndistortCameraOptions(),
+                                                  str(image_path), str(output_path))
+    ctl.Run()
+    return ctl
+
+
+def extract_colors(image_path, input_path, output_path, gpu_index=0):
+    """`colmap color_extractor` (exe/sfm.cc:208-228): reads the sparse model at input_path, gives every 3D point the mean
+    colour of its observations in the images under image_path, writes the model to output_path and returns it (needs an
+    MI355X)."""
+    import os
+    from . import color_extraction, workspace
+    model = workspace.read_sparse_model(str(input_path))
+    color_extraction.ExtractColorsForAllImages(model, str(image_path), gpu_index)
+    os.makedirs(str(output_path), exist_ok=True)
+    workspace.write_model_binary(model, str(output_path))
+    return model

@@ -3,8 +3,11 @@ start from (include/colmap_amd_undistort.h, colmap_amd/csrc/undistort.hip).
 
 Mirrors (reference file:line in each docstring):
   image/undistortion.{h,cc}            UndistortCameraOptions, UndistortCamera, UndistortImage, UndistortReconstruction
-  image/warp.{h,cc}                    WarpImageOptions
+  image/undistortion.{h,cc}            RectifyStereoCameras, RectifyAndUndistortStereoImages
+  image/warp.{h,cc}                    WarpImageOptions, WarpImageWithHomographyBetweenCameras
   controllers/undistorters.cc:150-313  COLMAPUndistorter
+  controllers/undistorters.cc:633-710  StandaloneImageUndistorter
+  controllers/undistorters.cc:712-820  StereoImageRectifier
 The camera arithmetic and every pixel run behind the C ABI (UndistortCamera on the host, the rest on the GPU); this
 module does the file side. There is no CPU fallback: without the library or a device the calls raise.
 """
@@ -41,6 +44,11 @@ class _Options(C.Structure):  # undistort_options
 class _Image(C.Structure):  # undistort_image
     _fields_ = [("camera", _Cam), ("data", C.c_void_p), ("channels", C.c_int32), ("reserved", C.c_int32),
                 ("out", C.c_void_p), ("out_capacity", C.c_size_t), ("out_camera", _Cam)]
+
+
+class _StereoPair(C.Structure):  # undistort_stereo_pair
+    _fields_ = [("image1", _Image), ("image2", _Image), ("R", C.c_double * 9), ("t", C.c_double * 3),
+                ("Q", C.c_double * 16)]
 
 
 def lib() -> C.CDLL:
@@ -198,6 +206,85 @@ def UndistortImage(options: UndistortCameraOptions, distorted_bitmap: np.ndarray
                    gpu_index: int = 0) -> Tuple[np.ndarray, W.SparseCamera]:
     """UndistortImage (image/undistortion.cc:266-301): (undistorted bitmap, undistorted camera)."""
     return UndistortImages(options, [distorted_bitmap], [distorted_camera], gpu_index)[0]
+
+
+def _fill_image(slot: _Image, bmp: np.ndarray, cam, out: np.ndarray):
+    slot.camera = _c_cam(cam)
+    slot.data = bmp.ctypes.data
+    slot.channels = 1 if bmp.ndim == 2 else bmp.shape[2]
+    slot.out = out.ctypes.data
+    slot.out_capacity = out.nbytes
+
+
+def _checked_bitmap(bmp, cam) -> np.ndarray:
+    bmp = np.ascontiguousarray(bmp, np.uint8)
+    if bmp.shape[:2] != (cam.height, cam.width):  # THROW_CHECK_EQ (image/undistortion.cc:271-272, :457-460)
+        raise UndistortError(f"bitmap {bmp.shape[1]}x{bmp.shape[0]} does not match its camera {cam.width}x{cam.height}")
+    return bmp
+
+
+def RectifyStereoCameras(camera1, camera2, R, t) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """RectifyStereoCameras (image/undistortion.cc:384-445) on the host side of the library: callable without a GPU.
+    cam2_from_cam1 as a 3x3 rotation R and a translation t; -> (H1, H2, Q)."""
+    R = np.ascontiguousarray(R, np.float64).reshape(3, 3)
+    t = np.ascontiguousarray(t, np.float64).reshape(3)
+    H1, H2, Q = np.empty((3, 3)), np.empty((3, 3)), np.empty((4, 4))
+    c1, c2 = _c_cam(camera1), _c_cam(camera2)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(lib().undistort_rectify_cameras(C.byref(c1), C.byref(c2), vp(R), vp(t), vp(H1), vp(H2), vp(Q)))
+    return H1, H2, Q
+
+
+def RectifyAndUndistortStereoImagePairs(options: UndistortCameraOptions, pairs: Sequence, gpu_index: int = 0) -> List:
+    """RectifyAndUndistortStereoImages for a batch in ONE undistort_rectify_images call: pairs holds
+    (bitmap1, bitmap2, camera1, camera2, R, t); -> [(undistorted1, undistorted2, undistorted_camera, Q)]."""
+    n = len(pairs)
+    arr = (_StereoPair * max(n, 1))()
+    keep = []
+    for i, (b1, b2, cam1, cam2, R, t) in enumerate(pairs):
+        b1, b2 = _checked_bitmap(b1, cam1), _checked_bitmap(b2, cam2)
+        want = UndistortCamera(options, cam1)  # camera 1 only (:462)
+        o1 = np.empty((want.height, want.width) + b1.shape[2:], np.uint8)
+        o2 = np.empty((want.height, want.width) + b2.shape[2:], np.uint8)
+        _fill_image(arr[i].image1, b1, cam1, o1)
+        _fill_image(arr[i].image2, b2, cam2, o2)
+        arr[i].R[:] = [float(v) for v in np.asarray(R, np.float64).reshape(9)]
+        arr[i].t[:] = [float(v) for v in np.asarray(t, np.float64).reshape(3)]
+        keep.append((b1, b2, o1, o2))
+    opt = _c_options(options)
+    _check(lib().undistort_rectify_images(C.byref(opt), C.c_int32(n), arr, C.c_int32(gpu_index)))
+    res = []
+    for i, (_, _, o1, o2) in enumerate(keep):
+        oc = _py_cam(arr[i].image1.out_camera, getattr(pairs[i][2], "camera_id", 0))
+        assert (oc.height, oc.width) == o1.shape[:2] == o2.shape[:2]
+        res.append((o1, o2, oc, np.array(arr[i].Q[:], np.float64).reshape(4, 4)))
+    return res
+
+
+def RectifyAndUndistortStereoImages(options: UndistortCameraOptions, distorted_image1: np.ndarray,
+                                    distorted_image2: np.ndarray, distorted_camera1, distorted_camera2, R, t,
+                                    gpu_index: int = 0):
+    """RectifyAndUndistortStereoImages (image/undistortion.cc:447-490) on the GPU:
+    -> (undistorted_image1, undistorted_image2, undistorted_camera, Q). When ShouldWarpDirectly is false the warp runs at
+    source size with the rescaled camera and the conjugated homography, then shrinks (include/colmap_amd_undistort.h)."""
+    return RectifyAndUndistortStereoImagePairs(options, [(distorted_image1, distorted_image2, distorted_camera1,
+                                                          distorted_camera2, R, t)], gpu_index)[0]
+
+
+def WarpImageWithHomographyBetweenCameras(options: WarpImageOptions, Hinv, source_camera, target_camera,
+                                          source_image: np.ndarray, gpu_index: int = 0) -> np.ndarray:
+    """WarpImageWithHomographyBetweenCameras (image/warp.cc:196-272), direct path, on the GPU: target pixel p takes the
+    source at ImgFromCam(source, CamFromImg(target, hnormalized(Hinv p))); 0 where the third coordinate is 0."""
+    bmp = _checked_bitmap(source_image, source_camera)
+    out = np.empty((target_camera.height, target_camera.width) + bmp.shape[2:], np.uint8)
+    im = _Image()
+    _fill_image(im, bmp, source_camera, out)
+    opt = _c_options(UndistortCameraOptions(warp_options=options))
+    H = np.ascontiguousarray(Hinv, np.float64).reshape(3, 3)
+    tgt = _c_cam(target_camera)
+    _check(lib().undistort_warp_homography(C.byref(opt), H.ctypes.data_as(C.c_void_p), C.byref(tgt), C.byref(im),
+                                           C.c_int32(gpu_index)))
+    return out
 
 
 def UndistortPoints(distorted_camera, undistorted_camera, xy: np.ndarray, gpu_index: int = 0) -> np.ndarray:
@@ -398,3 +485,124 @@ class COLMAPUndistorter:
                     f"  --PatchMatchStereo.max_image_size 2000 \\\n  --PatchMatchStereo.geom_consistency {g}\n")
             f.write("python -m colmap_amd stereo_fusion \\\n  --workspace_path . \\\n  --workspace_format COLMAP \\\n"
                     f"  --input_type {'geometric' if geometric else 'photometric'} \\\n  --output_path ./fused.ply\n")
+
+
+@dataclass
+class StereoImageRectifierOptions:
+    """StereoImageRectifier::Options (controllers/undistorters.h)."""
+    stereo_pairs: List[Tuple[int, int]] = field(default_factory=list)   # (image_id1, image_id2)
+    jpeg_quality: int = -1
+    gpu_index: int = 0
+    batch_size: int = 4  # (MI355X) pairs handed to one undistort_rectify_images call
+
+
+class StereoImageRectifier:
+    """StereoImageRectifier (controllers/undistorters.cc:712-820): per pair a directory `<name1>-<name2>` (`/` in names
+    replaced by `-`) with the two rectified, undistorted images and `Q.txt`."""
+
+    def __init__(self, options: StereoImageRectifierOptions, camera_options: UndistortCameraOptions, model: W.SparseModel,
+                 image_path: str, output_path: str):
+        if not -1 <= options.jpeg_quality <= 100:
+            raise UndistortError("Check failed: jpeg_quality in [-1, 100]")
+        self.options_, self.camera_options_, self.model_ = options, camera_options, model
+        self.image_path_, self.output_path_ = image_path, output_path
+        self.pair_names_: List[str] = []   # the pairs written
+
+    def Run(self):
+        os.makedirs(self.output_path_, exist_ok=True)
+        batch = []
+
+        def flush():
+            if not batch:
+                return
+            res = RectifyAndUndistortStereoImagePairs(self.camera_options_, [b[1] for b in batch], self.options_.gpu_index)
+            for (names, _), (o1, o2, _, Q) in zip(batch, res):
+                pair_name, n1, n2 = names
+                write_bitmap(os.path.join(self.output_path_, pair_name, n1), o1, self.options_.jpeg_quality)
+                write_bitmap(os.path.join(self.output_path_, pair_name, n2), o2, self.options_.jpeg_quality)
+                with open(os.path.join(self.output_path_, pair_name, "Q.txt"), "w") as f:   # WriteMatrix
+                    for row in Q:
+                        f.write(" ".join(repr(float(v)) for v in row) + "\n")
+                self.pair_names_.append(pair_name)
+            batch.clear()
+
+        for id1, id2 in self.options_.stereo_pairs:
+            image1, image2 = self.model_.images[id1], self.model_.images[id2]
+            cam1, cam2 = self.model_.cameras[image1.camera_id], self.model_.cameras[image2.camera_id]
+            n1, n2 = image1.name.replace("/", "-"), image2.name.replace("/", "-")
+            pair_name = f"{n1}-{n2}"
+            os.makedirs(os.path.join(self.output_path_, pair_name), exist_ok=True)
+            bitmaps = []
+            for img in (image1, image2):
+                src = os.path.join(self.image_path_, img.name)
+                bmp = read_bitmap(src)
+                if bmp is None:
+                    print(f"E Cannot read image at path {src}")
+                    break
+                bitmaps.append(bmp)
+            if len(bitmaps) != 2:
+                continue
+            # cam2_from_cam1 = image2.CamFromWorld() * Inverse(image1.CamFromWorld()) (:789-790)
+            R1, R2 = image1.RotationMatrix(), image2.RotationMatrix()
+            R = R2 @ R1.T
+            t = np.asarray(image2.tvec, np.float64) - R @ np.asarray(image1.tvec, np.float64)
+            batch.append(((pair_name, n1, n2), (bitmaps[0], bitmaps[1], cam1, cam2, R, t)))
+            if len(batch) >= self.options_.batch_size:
+                flush()
+        flush()
+
+
+@dataclass
+class StandaloneImageUndistorterOptions:
+    """StandaloneImageUndistorter::Options (controllers/undistorters.h)."""
+    image_names_and_cameras: List[Tuple[str, W.SparseCamera]] = field(default_factory=list)
+    copy_type: str = "copy"
+    jpeg_quality: int = -1
+    gpu_index: int = 0
+    batch_size: int = 8  # (MI355X) images handed to one undistort_images call
+
+
+class StandaloneImageUndistorter:
+    """StandaloneImageUndistorter (controllers/undistorters.cc:633-710): undistorts images whose cameras come from a
+    list, with no model on disk."""
+
+    def __init__(self, options: StandaloneImageUndistorterOptions, camera_options: UndistortCameraOptions, image_path: str,
+                 output_path: str):
+        if not -1 <= options.jpeg_quality <= 100:
+            raise UndistortError("Check failed: jpeg_quality in [-1, 100]")
+        self.options_, self.camera_options_ = options, camera_options
+        self.image_path_, self.output_path_ = image_path, output_path
+        self.image_names_: List[str] = []   # the images written
+
+    def Run(self):
+        os.makedirs(self.output_path_, exist_ok=True)
+        batch: List[Tuple[str, np.ndarray, W.SparseCamera]] = []
+
+        def flush():
+            if not batch:
+                return
+            res = UndistortImages(self.camera_options_, [b for _, b, _ in batch], [c for _, _, c in batch],
+                                  self.options_.gpu_index)
+            for (name, _, _), (bmp, _) in zip(batch, res):
+                if write_bitmap(os.path.join(self.output_path_, name), bmp, self.options_.jpeg_quality):
+                    self.image_names_.append(name)
+            batch.clear()
+
+        for name, cam in self.options_.image_names_and_cameras:
+            src, dst = os.path.join(self.image_path_, name), os.path.join(self.output_path_, name)
+            if os.path.dirname(name):
+                os.makedirs(os.path.dirname(dst), exist_ok=True)
+            if IsUndistorted(cam) and self.camera_options_.max_image_size < 0 and os.path.isfile(src):  # :684-690
+                _file_copy(src, dst, self.options_.copy_type)
+                self.image_names_.append(name)
+                continue
+            bmp = read_bitmap(src)
+            if bmp is None:
+                print(f"E Cannot read image at path {src}")
+                continue
+            if bmp.shape[:2] != (cam.height, cam.width):
+                raise UndistortError(f"image {name} is {bmp.shape[1]}x{bmp.shape[0]}, its camera {cam.width}x{cam.height}")
+            batch.append((name, bmp, cam))
+            if len(batch) >= self.options_.batch_size:
+                flush()
+        flush()

@@ -1,5 +1,6 @@
 // undistortion.hpp -- C++ host side of image undistortion (reference image/undistortion.h: UndistortCameraOptions,
-// UndistortCamera, UndistortImage, UndistortReconstruction; image/warp.h: WarpImageOptions) over the C ABI of
+// UndistortCamera, UndistortImage, UndistortReconstruction, RectifyStereoCameras, RectifyAndUndistortStereoImages;
+// image/warp.h: WarpImageOptions) over the C ABI of
 // colmap_amd_undistort.h. Header-only, standard library only.
 //
 //   colmap_amd::UndistortCameraOptions options;
@@ -120,6 +121,51 @@ inline void UndistortImage(const UndistortCameraOptions& options, const Bitmap& 
   undistorted_bitmap->height = im.out_camera.height;
   undistorted_bitmap->channels = distorted_bitmap.channels;
   undistorted_bitmap->data.resize(static_cast<size_t>(im.out_camera.width) * im.out_camera.height * distorted_bitmap.channels);
+}
+
+// RectifyStereoCameras (image/undistortion.cc:384-445): host only. cam2_from_cam1 as a row-major rotation R[9] and a
+// translation t[3]; H1, H2 (3x3) and Q (4x4) row-major.
+inline void RectifyStereoCameras(const Camera& camera1, const Camera& camera2, const double* R, const double* t,
+                                 double (*H1)[9], double (*H2)[9], double (*Q)[16]) {
+  const undistort_cam c1 = undistort_detail::ToC(camera1), c2 = undistort_detail::ToC(camera2);
+  undistort_detail::Check(undistort_rectify_cameras(&c1, &c2, R, t, *H1, *H2, *Q));
+}
+
+// RectifyAndUndistortStereoImages (image/undistortion.cc:447-490) on device options.gpu_index.
+inline void RectifyAndUndistortStereoImages(const UndistortCameraOptions& options, const Bitmap& distorted_image1,
+                                            const Bitmap& distorted_image2, const Camera& distorted_camera1,
+                                            const Camera& distorted_camera2, const double* R, const double* t,
+                                            Bitmap* undistorted_image1, Bitmap* undistorted_image2,
+                                            Camera* undistorted_camera, double (*Q)[16]) {
+  const Bitmap* in[2] = {&distorted_image1, &distorted_image2};
+  const Camera* cams[2] = {&distorted_camera1, &distorted_camera2};
+  Bitmap* out[2] = {undistorted_image1, undistorted_image2};
+  for (int s = 0; s < 2; ++s)
+    if (cams[s]->width != in[s]->width || cams[s]->height != in[s]->height ||
+        in[s]->data.size() != static_cast<size_t>(in[s]->width) * in[s]->height * in[s]->channels)
+      throw std::runtime_error("the bitmap does not match its camera");
+  const undistort_options o = undistort_detail::ToC(options);
+  const Camera target = UndistortCamera(options, distorted_camera1);
+  undistort_stereo_pair pair = {};
+  undistort_image* im[2] = {&pair.image1, &pair.image2};
+  for (int s = 0; s < 2; ++s) {
+    im[s]->camera = undistort_detail::ToC(*cams[s]);
+    im[s]->data = in[s]->data.data();
+    im[s]->channels = in[s]->channels;
+    out[s]->data.resize(static_cast<size_t>(target.width) * target.height * in[s]->channels);
+    im[s]->out = out[s]->data.data();
+    im[s]->out_capacity = out[s]->data.size();
+  }
+  for (int i = 0; i < 9; ++i) pair.R[i] = R[i];
+  for (int i = 0; i < 3; ++i) pair.t[i] = t[i];
+  undistort_detail::Check(undistort_rectify_images(&o, 1, &pair, options.gpu_index));
+  *undistorted_camera = undistort_detail::FromC(pair.image1.out_camera);
+  for (int s = 0; s < 2; ++s) {
+    out[s]->width = pair.image1.out_camera.width;
+    out[s]->height = pair.image1.out_camera.height;
+    out[s]->channels = in[s]->channels;
+  }
+  for (int i = 0; i < 16; ++i) (*Q)[i] = pair.Q[i];
 }
 
 // UndistortReconstruction (image/undistortion.cc:303-382) over caller arrays: cameras[i] is rewritten to PINHOLE (or a
