@@ -47,8 +47,12 @@ def test_generated_model_has_the_shapes():
     G.case_model_shape()
 
 
+def test_edges_model_has_the_observations_it_is_named_for():
+    G.case_edges_shape()
+
+
 @pytest.mark.parametrize("error_type", [Q.PIXEL, Q.NORMALIZED, Q.ANGULAR], ids=["pixel", "normalized", "angular"])
-@pytest.mark.parametrize("name", ["mixed", "single", "seam"])
+@pytest.mark.parametrize("name", ["mixed", "single", "seam", "edges"])
 def test_filter_all_points3D_matches_checker(name, error_type):
     G.case_filter_all(name, error_type)
 
@@ -57,7 +61,7 @@ def test_errors_then_angles():
     G.case_order_errors_then_angles()
 
 
-@pytest.mark.parametrize("name", ["mixed", "single"])
+@pytest.mark.parametrize("name", ["mixed", "single", "edges"])
 def test_negative_depth_matches_checker(name):
     G.case_negative_depth(name)
 
@@ -67,7 +71,7 @@ def test_short_tracks_match_checker(name):
     G.case_short_tracks(name)
 
 
-@pytest.mark.parametrize("name", ["mixed", "single", "seam"])
+@pytest.mark.parametrize("name", ["mixed", "single", "seam", "edges"])
 def test_point_errors_match_checker(name):
     G.case_point_errors(name)
 

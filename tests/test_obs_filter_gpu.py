@@ -7,7 +7,10 @@ within the bar of the camera models in fp64, 1e-6 px (tests/test_undistort_gpu.p
 by the largest focal length of the case, for ANGULAR (degrees) by the largest pixels-per-degree, i.e. the SMALLEST bar any
 camera of the case would give. Exact decisions only mean something away from the thresholds: the generator places every
 observation error, every decisive triangulation angle and every depth at least 1 % from its threshold, and each case
-asserts that first, on the checker's values. Nothing is excluded from the comparison."""
+asserts that first, on the checker's values. Nothing is excluded from the comparison.
+
+The model "edges" holds every camera model at 8 x its distortion and the observations at which a model has no projection
+or no inverse (edges_model, case_edges_shape)."""
 import numpy as np
 import pytest
 
@@ -161,6 +164,70 @@ def seam_model(seed=5):
     return b.rec
 
 
+EDGE_FEATURES = ("no_inverse_not_converged", "no_inverse_outside_eucm", "tiny_positive_depth", "behind_division_projects",
+                 "behind_opencv_does_not", "disc_sq_negative", "eucm_den_small", "fisheye_theta_beyond_half_pi")
+_EDGE_POINTS = {}
+
+
+def edges_model(seed=21):
+    """Every camera model at 8 x its distortion (tests/camera_edge_cases.py), EQUIRECTANGULAR, and the two cameras whose
+    forward domain ends at a finite angle for points in FRONT of them (DIVISION with k = +0.2, EUCM with alpha = 1.2,
+    beta = -0.3: at 8 x the suite's parameters neither rule can fire for w > 0). Each camera has two images, a point is
+    seen by the two images of one camera, and EDGE_FEATURES names the observations the model exists for (their point
+    ids are kept in _EDGE_POINTS; case_edges_shape restates each from the checker)."""
+    import camera_edge_cases as E
+    import undistort_reference as R
+    b = Builder([], seed)
+    rng = b.rng
+    cams = []
+    for m in G.PERSPECTIVE_MODELS:
+        c = G.strong(G.ba_camera(m), 8.0)
+        cams.append((m, c.width, c.height, c.params))
+    cams.append((scene.EQUIRECTANGULAR, EQUI.width, EQUI.height, EQUI.params))
+    for name in ("forward-DIVISION-k0.2", "forward-EUCM-1.2--0.3"):
+        c = E.case(name).cam
+        cams.append((c.model_id, c.width, c.height, c.params))
+    for k, (m, w, h, p) in enumerate(cams):
+        b.rec.cameras[k + 1] = scene.Camera(k + 1, m, w, h, np.array(p, np.float64))
+    b.ncam = len(cams)
+    # identity rotations: a point's camera coordinates in the first image are its world coordinates
+    pair = {cid: [b.add_image([0, 0, 0, 1, 0.0, 0.0, 0.0], cid), b.add_image([0, 0, 0, 1, 0.3, -0.2, 0.1], cid)]
+            for cid in b.rec.cameras}
+    first = {}
+    for cid, c in b.rec.cameras.items():
+        first.setdefault(c.model_id, cid)
+    for cid in b.rec.cameras:
+        for k in range(36):                                  # a 6 x 6 fan of bearings out to |u| = 1, |v| = 0.8
+            u = (k % 6 - 2.5) * 0.4 + rng.uniform(-0.05, 0.05)
+            v = (k // 6 - 2.5) * 0.32 + rng.uniform(-0.05, 0.05)
+            z = rng.uniform(3.0, 5.0)
+            b.add_point([u * z, v * z, z], pair[cid], {0} if k % 9 == 4 else ())
+        for _ in range(2):                                   # low parallax: 0.37 / 400 rad
+            b.add_point([rng.uniform(-20, 20), rng.uniform(-20, 20), 400.0], pair[cid])
+
+    def special(feature, model, xyz, pixel=None, camera_id=None):
+        cid = camera_id or first[model]
+        pid = b.add_point(xyz, pair[cid])
+        if pixel is not None:
+            im, idx = b.rec.points3D[pid].track[0]
+            b.rec.images[im].points2D[idx].xy = np.array(pixel, np.float64)
+        _EDGE_POINTS[feature] = pid
+
+    full = b.rec.cameras[first[scene.FULL_OPENCV]]
+    lost = np.isnan(R.cam_from_img(R.Camera(full.model_id, full.width, full.height, full.params), E.ITERATIVE_GRID)[:, 0])
+    special("no_inverse_not_converged", scene.FULL_OPENCV, [0.4, 0.4, 4.0], E.ITERATIVE_GRID[np.nonzero(lost)[0][0]])
+    special("no_inverse_outside_eucm", scene.EUCM, [0.4, -0.4, 4.0], [-4000.0, 384.0])
+    special("tiny_positive_depth", scene.SIMPLE_RADIAL, [0.3, 0.2, 1e-17])
+    special("behind_division_projects", scene.DIVISION, [0.4, -0.3, -2.0])
+    special("behind_opencv_does_not", scene.OPENCV, [0.4, -0.3, -2.0])
+    special("disc_sq_negative", scene.DIVISION, [6.0, 2.0, 4.0], camera_id=b.ncam - 1)
+    special("eucm_den_small", scene.EUCM, [1.81 * 4.0, 0.0, 4.0], camera_id=b.ncam)
+    fish = b.rec.cameras[first[scene.FISHEYE]]
+    special("fisheye_theta_beyond_half_pi", scene.FISHEYE, [0.5, 0.1, 4.0],
+            [fish.params[2] + 1.7 * fish.params[0] * np.cos(0.4), fish.params[3] + 1.7 * fish.params[1] * np.sin(0.4)])
+    return b.rec
+
+
 _MODELS = {}
 
 
@@ -168,7 +235,7 @@ def model(name):
     """Built once and never changed: every case works on copies."""
     if name not in _MODELS:
         _MODELS[name] = {"mixed": lambda: build_model(ALL_MODELS, 11), "single": lambda: build_model([scene.SIMPLE_RADIAL], 12),
-                         "seam": seam_model, "empty": scene.Reconstruction}[name]()
+                         "seam": seam_model, "edges": edges_model, "empty": scene.Reconstruction}[name]()
     return _MODELS[name]
 
 
@@ -272,6 +339,46 @@ def case_model_shape():
     for lo, hi, per_block in ((0, 16, 256), (17, 64, 16), (65, 10 ** 9, 4)):
         n = int(((lengths >= lo) & (lengths <= hi)).sum())
         assert n > per_block and n % per_block != 0, (lo, hi, n)
+
+
+def case_edges_shape():
+    """What the "edges" model must contain, restated from the checker and the model alone."""
+    import undistort_reference as R
+    rec = model("edges")
+    assert {c.model_id for c in rec.cameras.values()} == set(ALL_MODELS) and len(rec.cameras) == 20
+    assert all(len(p.track) == 2 for p in rec.points3D.values())
+    per_camera = np.bincount([rec.images[p.track[0][0]].camera_id for p in rec.points3D.values()], minlength=21)[1:]
+    assert (per_camera >= 38).all() and (per_camera <= 42).all()
+    assert set(_EDGE_POINTS) == set(EDGE_FEATURES)
+
+    def first_observation(feature):
+        pt = rec.points3D[_EDGE_POINTS[feature]]
+        im, idx = pt.track[0]
+        img = rec.images[im]
+        cam = rec.cameras[img.camera_id]
+        return cam, Q.point_in_cam(img, pt.xyz), img.points2D[idx].xy
+
+    def inverse(cam, xy):
+        return R.cam_from_img(R.Camera(cam.model_id, cam.width, cam.height, cam.params), xy[None])[0]
+
+    for feature in ("no_inverse_not_converged", "no_inverse_outside_eucm"):
+        cam, _, xy = first_observation(feature)
+        assert np.isnan(inverse(cam, xy)).all(), feature
+    cam, pc, _ = first_observation("tiny_positive_depth")
+    assert 0.0 < pc[2] < Q.EPS and Q.img_from_cam(cam, pc) is None
+    cam, pc, _ = first_observation("behind_division_projects")
+    assert cam.model_id == scene.DIVISION and pc[2] < 0 and np.isfinite(Q.img_from_cam(cam, pc)).all()
+    cam, pc, _ = first_observation("behind_opencv_does_not")
+    assert cam.model_id == scene.OPENCV and pc[2] < 0 and Q.img_from_cam(cam, pc) is None
+    cam, pc, _ = first_observation("disc_sq_negative")
+    assert pc[2] > Q.EPS and pc[2] ** 2 - 4.0 * (pc[0] ** 2 + pc[1] ** 2) * cam.params[4] < -1.0 and Q.img_from_cam(cam, pc) is None
+    cam, pc, _ = first_observation("eucm_den_small")
+    rho2 = cam.params[5] * (pc[0] ** 2 + pc[1] ** 2) + pc[2] ** 2
+    assert pc[2] > Q.EPS and rho2 > 0.01 and cam.params[4] * np.sqrt(rho2) + (1.0 - cam.params[4]) * pc[2] < -0.01
+    assert Q.img_from_cam(cam, pc) is None
+    cam, _, xy = first_observation("fisheye_theta_beyond_half_pi")
+    theta = np.hypot((xy[0] - cam.params[2]) / cam.params[0], (xy[1] - cam.params[3]) / cam.params[1])
+    assert theta > np.pi / 2 + 0.1 and np.isfinite(inverse(cam, xy)).all()
 
 
 def case_filter_all(name, error_type):
@@ -420,8 +527,12 @@ def test_generated_model_has_the_shapes():
     case_model_shape()
 
 
+def test_edges_model_has_the_observations_it_is_named_for():
+    case_edges_shape()
+
+
 @pytest.mark.parametrize("error_type", [Q.PIXEL, Q.NORMALIZED, Q.ANGULAR], ids=["pixel", "normalized", "angular"])
-@pytest.mark.parametrize("name", ["mixed", "single", "seam"])
+@pytest.mark.parametrize("name", ["mixed", "single", "seam", "edges"])
 def test_filter_all_points3D_matches_checker(name, error_type):
     case_filter_all(name, error_type)
 
@@ -430,7 +541,7 @@ def test_errors_then_angles():
     case_order_errors_then_angles()
 
 
-@pytest.mark.parametrize("name", ["mixed", "single"])
+@pytest.mark.parametrize("name", ["mixed", "single", "edges"])
 def test_negative_depth_matches_checker(name):
     case_negative_depth(name)
 
@@ -440,7 +551,7 @@ def test_short_tracks_match_checker(name):
     case_short_tracks(name)
 
 
-@pytest.mark.parametrize("name", ["mixed", "single", "seam"])
+@pytest.mark.parametrize("name", ["mixed", "single", "seam", "edges"])
 def test_point_errors_match_checker(name):
     case_point_errors(name)
 

@@ -165,8 +165,19 @@ def img_from_normalized(cam, u, v):
         return f1 * (u + du) + c1, f2 * (v + dv) + c2, ok
 
 
-def iterative_undistortion(model, e, u, v):
-    """IterativeUndistortion (sensor/models.h:1141-1197), all points at once; Jacobian by complex step."""
+class NewtonTrace:
+    """Per point of one iterative_undistortion call: the iterations taken, the steps the trust region shortened, the
+    steps at which elimination with partial pivoting would swap its rows (|J10| > |J00|), and those of them at which
+    elimination WITHOUT the swap would divide by (nearly) nothing (|J00| <= 1e-12 |J10|)."""
+
+    def __init__(self, n):
+        self.iterations, self.clamped, self.row_swaps, self.tiny_pivots = (np.zeros(n, np.int64) for _ in range(4))
+        self.converged = np.zeros(n, bool)
+
+
+def iterative_undistortion(model, e, u, v, trace=None):
+    """IterativeUndistortion (sensor/models.h:1141-1197), all points at once; Jacobian by complex step. `trace`, a
+    NewtonTrace of the same length, is filled in when given; the values do not depend on it."""
     x0, y0 = u.copy(), v.copy()
     x, y = u.copy(), v.copy()
     done = np.zeros(u.shape, bool)
@@ -192,12 +203,19 @@ def iterative_undistortion(model, e, u, v):
             radius_sqr = np.maximum((xa * xa + ya * ya) * 0.1 * 0.1, 0.1 * 0.1)
             n2 = sx * sx + sy * sy
             s = np.where(n2 > radius_sqr, np.sqrt(radius_sqr / n2), 1.0)
+            if trace is not None:
+                trace.iterations[act] += 1
+                trace.clamped[act] += n2 > radius_sqr
+                trace.row_swaps[act] += np.abs(J[..., 1, 0]) > np.abs(J[..., 0, 0])
+                trace.tiny_pivots[act] += np.abs(J[..., 0, 0]) <= 1e-12 * np.abs(J[..., 1, 0])
             sx, sy = sx * s, sy * s
             x[act] = xa - sx
             y[act] = ya - sy
             fin = np.zeros(u.shape, bool)
             fin[act] = sx * sx + sy * sy < 1e-10
             done |= fin
+    if trace is not None:
+        trace.converged[:] = done
     return x, y, done
 
 
