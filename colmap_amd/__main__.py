@@ -12,6 +12,9 @@ COMMANDS = {
                                      "undistort images whose cameras come from a text list (exe/image.cc:427-523)"),
     "image_rectifier": ("colmap_amd.image_rectifier", "rectify and undistort stereo pairs, write Q (exe/image.cc:211-251)"),
     "color_extractor": ("colmap_amd.color_extractor", "colour the 3D points of a sparse model from its images (exe/sfm.cc:208-228)"),
+    "model_comparer": ("colmap_amd.model_comparer", "align two sparse models and report per-image pose errors (exe/model.cc:520-631)"),
+    "model_aligner": ("colmap_amd.model_aligner", "move a sparse model onto reference camera positions (exe/model.cc:257-424)"),
+    "model_transformer": ("colmap_amd.model_transformer", "apply a stored similarity to a sparse model or a PLY (exe/model.cc:1081-1129)"),
 }
 
 

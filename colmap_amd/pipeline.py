@@ -128,3 +128,46 @@ def extract_colors(image_path, input_path, output_path, gpu_index=0):
     os.makedirs(str(output_path), exist_ok=True)
     workspace.write_model_binary(model, str(output_path))
     return model
+
+
+def align_reconstructions_via_reprojections(src_reconstruction, tgt_reconstruction, min_inlier_observations=0.3,
+                                            max_reproj_error=8.0, gpu_index=0):
+    """pycolmap.align_reconstructions_via_reprojections (estimators/alignment.cc:301-342): tgt_from_src as an
+    alignment.Sim3d, or None; the hypotheses are scored on the GPU (needs an MI355X)."""
+    from . import alignment
+    return alignment.AlignReconstructionsViaReprojections(src_reconstruction, tgt_reconstruction, min_inlier_observations,
+                                                          max_reproj_error, gpu_index=gpu_index)
+
+
+def align_reconstructions_via_proj_centers(src_reconstruction, tgt_reconstruction, max_proj_center_error, gpu_index=0):
+    """pycolmap.align_reconstructions_via_proj_centers (alignment.cc:344-369): tgt_from_src or None."""
+    from . import alignment
+    return alignment.AlignReconstructionsViaProjCenters(src_reconstruction, tgt_reconstruction, max_proj_center_error,
+                                                        gpu_index=gpu_index)
+
+
+def align_reconstructions_via_points(src_reconstruction, tgt_reconstruction, min_common_observations=3, max_error=0.005,
+                                     min_inlier_ratio=0.9, gpu_index=0):
+    """pycolmap.align_reconstructions_via_points (alignment.cc:400-458): tgt_from_src or None."""
+    from . import alignment
+    return alignment.AlignReconstructionsViaPoints(src_reconstruction, tgt_reconstruction, min_common_observations, max_error,
+                                                   min_inlier_ratio, gpu_index)
+
+
+def align_reconstruction_to_locations(src, tgt_image_names, tgt_image_locations, min_common_images, ransac_options,
+                                      src_names=None, gpu_index=0):
+    """pycolmap.align_reconstruction_to_locations (alignment.cc:185-238): tgt_from_src or None. A scene.Reconstruction
+    carries no image names: give them as `src_names` (image_id -> name), or use image ids as names."""
+    from . import alignment
+    return alignment.AlignReconstructionToLocations(src, tgt_image_names, tgt_image_locations, min_common_images,
+                                                    ransac_options, src_names, gpu_index)
+
+
+def compare_reconstructions(reconstruction1, reconstruction2, alignment_error="reprojection", min_inlier_observations=0.3,
+                            max_reproj_error=8.0, max_proj_center_error=0.1, names1=None, names2=None, gpu_index=0):
+    """pycolmap.compare_reconstructions (CompareModels, exe/model.cc:575-631): a dict with rec2_from_rec1 and the
+    per-image errors, or None where the alignment fails."""
+    from . import model_comparer
+    result = model_comparer.compare_models(reconstruction1, reconstruction2, names1, names2, alignment_error,
+                                           min_inlier_observations, max_reproj_error, max_proj_center_error, gpu_index)
+    return None if result is None else {"rec2_from_rec1": result[1], "errors": result[0]}
