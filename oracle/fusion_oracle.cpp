@@ -484,7 +484,7 @@ struct Fuser {
   static constexpr unsigned long long kCommitted = ~0ull;
   struct Node { int image, pix, level; };
   struct Rec { int image, pix; bool in_box; };
-  struct WalkRec { long long tau; int first, count; };
+  struct WalkRec { long long tau; int first, count; long long deepest; };
   struct Lane {  // one pool thread = one wave of fusion.hip
     std::vector<Rec> rec;
     std::vector<WalkRec> walks;
@@ -496,6 +496,13 @@ struct Fuser {
   int simT = 1;
   unsigned long long rstar = 0;
   long long passes_run = 0, walks_run = 0, walks_discarded = 0, conflicts = 0, cuts = 0;
+  // extremes of the input under these options (fuo_last_extremes): they only observe -- what decides which capacity of
+  // fusion.hip a run reaches: the deepest stack of any walk (entries after an expansion's pushes = the kernel's `sp` of
+  // the depth-first walk; speculative walks included, which depend on the interleaving), the same over the committed
+  // walks alone (a committed walk saw the sequential masks: every execution of the schedule repeats it entry for
+  // entry), the largest in-box support of a committed walk (values per median), the most pixels the committed walks of
+  // one image step recorded (what ONE wave records when it takes the whole step in one pass)
+  long long deepest_stack = 0, deepest_committed_stack = 0, largest_support = 0, largest_step_records = 0;
   double model_us = 0.0;  // critical path under a latency model: per pass max over waves of (3 us per absorbed pixel + 1 us per 64 scanned turns) + 40 us
 
   bool MaskedFor(unsigned long long w, int t) const {
@@ -555,6 +562,7 @@ struct Fuser {
     Node cand{I, seed, 0};
     size_t n_in = 0;
     int recorded = 0;
+    long long walk_deepest = 0;
     for (;;) {
       float normal[3], xyz[3];
       bool in_box;
@@ -604,6 +612,8 @@ struct Fuser {
           if (!PassesStatic(next, q, ref_point, ref_normal)) continue;
           stack.push_back({next, q, cand.level + 1});
         }
+        walk_deepest = std::max<long long>(walk_deepest, (long long)stack.size());
+        deepest_stack = std::max(deepest_stack, walk_deepest);
       }
       bool found = false;
       while (!stack.empty() && !found) {
@@ -615,7 +625,7 @@ struct Fuser {
       }
       if (!found) break;
     }
-    ln.walks.push_back({tau, (int)first, (int)(ln.rec.size() - first)});
+    ln.walks.push_back({tau, (int)first, (int)(ln.rec.size() - first), walk_deepest});
     return true;
   }
 
@@ -645,6 +655,8 @@ struct Fuser {
       cr.push_back(color[0]); cg.push_back(color[1]); cb.push_back(color[2]);
       if (std::find(vis.begin(), vis.end(), q.image) == vis.end()) vis.push_back(q.image);
     }
+    largest_support = std::max<long long>(largest_support, (long long)px.size());
+    deepest_committed_stack = std::max(deepest_committed_stack, wr.deepest);
     Emit(px, py, pz, nx, ny, nz, cr, cg, cb, vis, dst);
   }
 
@@ -676,7 +688,7 @@ struct Fuser {
         const unsigned long long r_end = (unsigned long long)pl.ticks() * T;
         FU_CHECK(r_end < 0xFFFFFFF0ull, "turns of one image < 2^32");
         unsigned long long r_next = 0;
-        long long P = p_first;
+        long long P = p_first, step_records = 0;
         while (r_next < r_end) {
           FU_CHECK(epoch < 0xFFFFFFFEu, "epoch counter");
           const long long tau0 = (long long)(r_next / T), tau_end = std::min(tau0 + P, pl.ticks());
@@ -721,8 +733,10 @@ struct Fuser {
             const Lane& ln = lanes[t];
             worst = std::max(worst, 3.0 * ln.nodes + ln.scans / 64.0);
             for (const WalkRec& wr : ln.walks) {
-              if ((unsigned long long)wr.tau * T + t < rstar) CommitWalk(ln, wr, &per_thread[t]);
-              else ++walks_discarded;
+              if ((unsigned long long)wr.tau * T + t < rstar) {
+                CommitWalk(ln, wr, &per_thread[t]);
+                step_records += wr.count;
+              } else ++walks_discarded;
             }
           }
           model_us += worst + 40.0;
@@ -733,6 +747,7 @@ struct Fuser {
           ++epoch;
           ++passes_run;
         }
+        largest_step_records = std::max(largest_step_records, step_records);
       }
       fused[I] = 1;
     }
@@ -742,6 +757,7 @@ struct Fuser {
 
 long long g_rounds = 0, g_walks = 0, g_discarded = 0, g_conflicts = 0, g_cuts = 0;
 double g_model_us = 0.0;
+long long g_deepest_stack = 0, g_deepest_committed_stack = 0, g_largest_support = 0, g_largest_step_records = 0;
 
 template <typename F>
 int Guard(F&& f) {
@@ -808,6 +824,10 @@ FUO_API int fuo_run(int32_t mode, const fusion_options* options, int32_t num_ima
     g_conflicts = fuser.conflicts;
     g_cuts = fuser.cuts;
     g_model_us = fuser.model_us;
+    g_deepest_stack = fuser.deepest_stack;
+    g_deepest_committed_stack = fuser.deepest_committed_stack;
+    g_largest_support = fuser.largest_support;
+    g_largest_step_records = fuser.largest_step_records;
   });
   if (rc != 0) {
     delete r;
@@ -848,6 +868,15 @@ FUO_API void fuo_last_schedule(long long* discarded, long long* conflicts, long 
   *conflicts = g_conflicts;
   *cuts = g_cuts;
   *model_us = g_model_us;
+}
+
+// mode 2: the extremes of the last run (zero after the other modes) -- properties of the input and the options
+FUO_API void fuo_last_extremes(long long* deepest_stack, long long* deepest_committed_stack, long long* largest_support,
+                               long long* largest_step_records) {
+  *deepest_stack = g_deepest_stack;
+  *deepest_committed_stack = g_deepest_committed_stack;
+  *largest_support = g_largest_support;
+  *largest_step_records = g_largest_step_records;
 }
 
 FUO_API const char* fuo_last_error(void) { return g_error.c_str(); }

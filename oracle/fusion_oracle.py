@@ -6,6 +6,7 @@
                                                       mode 2: simulation of fusion.hip's passes (== mode 1)
 
     fuse_census(options, images, overlapping_images, mode=1)   the same through the census build: (points, counts)
+    fuse_extremes(options, images, overlapping_images)         mode 2 and its extremes: (points, {deepest stack, ...})
 
 Takes the same arguments as colmap_amd.fusion.fuse and reuses its marshalling, so both sides see the
 identical structs.
@@ -67,6 +68,21 @@ class _EntryPoints:
 def fuse(options, images, overlapping_images, mode):
     from colmap_amd import fusion
     return fusion.fuse(options, images, overlapping_images, entry_points=_EntryPoints(mode))
+
+
+EXTREME_FIELDS = ("deepest_stack", "deepest_committed_stack", "largest_support", "largest_step_records")
+
+
+def fuse_extremes(options, images, overlapping_images):
+    """fuse() in mode 2, and what that run says about the input under these options: (points, {deepest_stack: entries
+    on the stack of any walk after an expansion's pushes, deepest_committed_stack: the same over the committed walks
+    (which every execution of the schedule repeats entry for entry; speculative walks depend on timing),
+    largest_support: in-box pixels of a committed walk, largest_step_records: pixels recorded by the committed walks of one image step}). They decide which capacities of
+    fusion.hip a run reaches (tests/fusion_capacity_cases.py); they never change a result."""
+    out = fuse(options, images, overlapping_images, mode=2)
+    vals = [C.c_longlong() for _ in EXTREME_FIELDS]
+    lib().fuo_last_extremes(*[C.byref(v) for v in vals])
+    return out, dict(zip(EXTREME_FIELDS, (v.value for v in vals)))
 
 
 def fuse_census(options, images, overlapping_images, mode=1):
