@@ -15,6 +15,16 @@ COMMANDS = {
     "model_comparer": ("colmap_amd.model_comparer", "align two sparse models and report per-image pose errors (exe/model.cc:520-631)"),
     "model_aligner": ("colmap_amd.model_aligner", "move a sparse model onto reference camera positions (exe/model.cc:257-424)"),
     "model_transformer": ("colmap_amd.model_transformer", "apply a stored similarity to a sparse model or a PLY (exe/model.cc:1081-1129)"),
+    "exhaustive_matcher": ("colmap_amd.exhaustive_matcher", "match the SIFT descriptors of all image pairs of a database (exe/feature.cc:120-143)"),
+    "sequential_matcher": ("colmap_amd.sequential_matcher", "match every image with the next ones in name order (exe/feature.cc:270-297)"),
+    "matches_importer": ("colmap_amd.matches_importer", "match the image pairs a text file lists (exe/feature.cc:226-268)"),
+}
+
+# matcher commands of the reference whose pairing is not built: named so that the message says what is missing
+NOT_BUILT = {
+    "vocab_tree_matcher": "vocabulary-tree pairing needs the visual index and its retrieval, which are missing",
+    "spatial_matcher": "spatial pairing needs pose priors and a nearest-neighbour search over positions, which are missing",
+    "transitive_matcher": "transitive pairing needs the graph of existing two-view geometries, which are never written here",
 }
 
 
@@ -25,6 +35,10 @@ def main(argv=None) -> int:
         for name, (_, what) in COMMANDS.items():
             print(f"  {name:28s} {what}")
         return 0
+    if argv[0] in NOT_BUILT:
+        print(f"E Command `{argv[0]}` is not built: {NOT_BUILT[argv[0]]}. exhaustive_matcher, sequential_matcher and "
+              "matches_importer --match_type pairs are.", file=sys.stderr)
+        return 1
     if argv[0] not in COMMANDS:
         print(f"E Command `{argv[0]}` not recognized. To list the available commands, run `python -m colmap_amd help`.",
               file=sys.stderr)

@@ -171,3 +171,24 @@ def compare_reconstructions(reconstruction1, reconstruction2, alignment_error="r
     result = model_comparer.compare_models(reconstruction1, reconstruction2, names1, names2, alignment_error,
                                            min_inlier_observations, max_reproj_error, max_proj_center_error, gpu_index)
     return None if result is None else {"rec2_from_rec1": result[1], "errors": result[0]}
+
+
+def match_exhaustive(database_path, matching_options=None, block_size=50, gpu_index=0, cache_bytes=0, batch_pairs=None):
+    """pycolmap.match_exhaustive (ExhaustiveFeatureMatcher, controllers/feature_matching.cc) without geometric
+    verification: matches all image pairs of the database on the GPU (needs an MI355X) and writes the `matches` table;
+    no `two_view_geometries` row is written. matching_options: a feature_matching.SiftMatchingOptions. Returns the
+    counts of pairs matched and skipped."""
+    from . import database, feature_matching as fm
+    with database.Database(database_path) as db:
+        blocks = fm.exhaustive_pair_blocks(db.read_image_ids(), block_size)
+        return fm.match_blocks(db, blocks, matching_options, gpu_index, cache_bytes, batch_pairs or fm.DEFAULT_BATCH_PAIRS)
+
+
+def match_sequential(database_path, matching_options=None, overlap=10, quadratic_overlap=True, gpu_index=0, cache_bytes=0,
+                     batch_pairs=None):
+    """pycolmap.match_sequential (SequentialFeatureMatcher) without loop detection and geometric verification: every
+    image, in name order, with its next `overlap` images (or 1, 2, 4, ... places later)."""
+    from . import database, feature_matching as fm
+    with database.Database(database_path) as db:
+        blocks = fm.sequential_pair_blocks(fm.order_by_name(db.read_image_names()), overlap, quadratic_overlap)
+        return fm.match_blocks(db, blocks, matching_options, gpu_index, cache_bytes, batch_pairs or fm.DEFAULT_BATCH_PAIRS)
