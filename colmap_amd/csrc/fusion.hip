@@ -35,6 +35,11 @@
 //             neighbour loads are in flight, the entry pushed last taken without a second look.
 //   compact   per image, a device scan in (thread, tick) order; the host concatenates per thread.
 //
+// The device code in order: the mask words and the stack; "steps every traversal runs" -- back-projection, box test,
+// normal rotation, neighbour test, conflict cut, walk record, mark encoding, each stated once; the three traversals that
+// are made of them (walk_turn depth-first, walk_turn_wide breadth-first, seed_group several start pixels at once) and
+// take_turn, which chooses between them; fusion_walk_kernel; the medians and fusion_commit_kernel; the compaction.
+//
 // The checker is oracle/fusion_oracle.cpp: mode 1 runs the reference's Fuse() sequentially in the same
 // order (tests/test_fusion.py compares bit for bit), mode 2 simulates the passes above with the waves
 // interleaved at random, mode 0 is row-major (= num_threads 1). All arithmetic is float / double as the
@@ -166,12 +171,6 @@ __device__ inline unsigned long long ld_word(const unsigned long long* p) {  // 
 }
 __device__ inline unsigned ld_u32(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// masked for pool thread t: committed, or a tentative mark of this pass made by t itself
-__device__ inline bool masked_for(unsigned long long w, unsigned epoch, unsigned T, unsigned t) {
-  if (w == kCommitted) return true;
-  return (unsigned)(w >> 32) == epoch && (0xFFFFFFFFu - (unsigned)w) % T == t;
-}
-
 __device__ inline int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ inline unsigned uniform(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ inline float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
@@ -239,10 +238,132 @@ __device__ inline void note_window_pixel(const Params& p, const WaveStack& st, u
   if (d < (unsigned)kWave) __hip_atomic_fetch_or(st.win, 1ull << d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// ---- steps every traversal runs ----
+// The depth-first walk (walk_turn), the breadth-first walk (walk_turn_wide) and the group of start pixels (seed_group)
+// differ in WHICH pixels they look at together, not in what they do with one: each step below states the reference's
+// arithmetic (fusion.cc:401-489) or the pass protocol once. None of them knows its caller; what differs is an argument.
+
+// the mark of the turn `rank` of this pass (atomicMax: the lowest rank keeps the word), and the rank of a mark
+__device__ __forceinline__ unsigned long long mark_key(unsigned epoch, unsigned rank) {
+  return ((unsigned long long)epoch << 32) | (unsigned long long)(0xFFFFFFFFu - rank);
+}
+__device__ __forceinline__ unsigned mark_rank(unsigned long long w) { return 0xFFFFFFFFu - (unsigned)w; }
+
+// masked for pool thread t: committed, or a tentative mark of this pass made by t itself
+__device__ __forceinline__ bool masked_for(unsigned long long w, unsigned epoch, unsigned T, unsigned t) {
+  if (w == kCommitted) return true;
+  return (unsigned)(w >> 32) == epoch && mark_rank(w) % T == t;
+}
+
+// how many lanes below `lane` are set in the ballot m: the lane's position among them
+__device__ __forceinline__ int lane_pos(unsigned long long m, int lane) { return __popcll(m & ((1ull << lane) - 1ull)); }
+
+// pixel and depth to the point in the world (fusion.cc:437-445)
+__device__ __forceinline__ void back_project(const DevImage& im, int pix, float depth, float xyz[3]) {
+  const int row = pix / im.dw, col = pix - row * im.dw;
+  const float hx = (float)col * depth, hy = (float)row * depth;
+  for (int r = 0; r < 3; ++r)
+    xyz[r] = im.inv_P[4 * r] * hx + im.inv_P[4 * r + 1] * hy + im.inv_P[4 * r + 2] * depth + im.inv_P[4 * r + 3] * 1.0f;
+}
+
+__device__ __forceinline__ bool in_box(const Params& p, const float xyz[3]) {
+  return !(xyz[0] < p.bmin[0] || xyz[1] < p.bmin[1] || xyz[2] < p.bmin[2] || xyz[0] > p.bmax[0] || xyz[1] > p.bmax[1] ||
+           xyz[2] > p.bmax[2]);
+}
+
+// a normal of the image's normal map, rotated into the world (the caller has loaded it: the loads go out with its others)
+__device__ __forceinline__ void rotate_normal(const DevImage& im, float nl0, float nl1, float nl2, float n[3]) {
+  for (int r = 0; r < 3; ++r) n[r] = im.inv_R[3 * r] * nl0 + im.inv_R[3 * r + 1] * nl1 + im.inv_R[3 * r + 2] * nl2;
+}
+
+// The neighbour of the pixel goff (at xyz) in image `next` (fusion.cc:474-488), and the tests of fusion.cc:407-447 that do
+// not depend on the masks, against the point `ref` and normal `refn` the walk started from. pass: it goes on the stack
+// (qoff, q, d = its word offset, pixel and depth) -- it passed them and is not masked for pool thread t now.
+struct Neighbour {
+  bool pass;
+  unsigned long long qoff;
+  int q, next;
+  float d;
+};
+__device__ __forceinline__ Neighbour test_neighbour(const Params& p, const WalkTables& tb, unsigned t, int next, unsigned long long goff,
+                                                    const float xyz[3], const float ref[3], const float refn[3]) {
+  Neighbour nb{false, 0ull, 0, next, 0.0f};
+  const DevImage& nx = tb.images[next];
+  if (nx.pos >= p.step) {  // used, and not fused in an earlier step
+    float np[3];
+    for (int r = 0; r < 3; ++r) np[r] = nx.P[4 * r] * xyz[0] + nx.P[4 * r + 1] * xyz[1] + nx.P[4 * r + 2] * xyz[2] + nx.P[4 * r + 3];
+    const float fcol = roundf(np[0] / np[2]), frow = roundf(np[1] / np[2]);
+    if (fcol >= 0.0f && frow >= 0.0f && fcol < (float)nx.dw && frow < (float)nx.dh) {
+      const int qcol = (int)fcol, qrow = (int)frow;
+      nb.q = qrow * nx.dw + qcol;
+      nb.qoff = (unsigned long long)nx.pix_off + (unsigned long long)nb.q;
+      const unsigned long long w = ld_word(p.word + nb.qoff);
+      nb.d = p.depth[nb.qoff];
+      const float* nl = p.normal + 3 * nb.qoff;
+      const float nl0 = nl[0], nl1 = nl[1], nl2 = nl[2];
+      // (qoff != goff: the pixel being expanded -- an image listed as its own neighbour -- is masked by the
+      // mark issued a moment ago, which this load is not ordered behind)
+      if (nb.qoff != goff && !masked_for(w, p.epoch, (unsigned)p.T, t) && !(nb.d <= 0.0f)) {
+        float proj[3];
+        for (int r = 0; r < 3; ++r)
+          proj[r] = nx.P[4 * r] * ref[0] + nx.P[4 * r + 1] * ref[1] + nx.P[4 * r + 2] * ref[2] + nx.P[4 * r + 3] * 1.0f;
+        const float depth_error = fabsf((proj[2] - nb.d) / nb.d);
+        const float col_diff = proj[0] / proj[2] - (float)qcol;
+        const float row_diff = proj[1] / proj[2] - (float)qrow;
+        float nrm[3];
+        rotate_normal(nx, nl0, nl1, nl2, nrm);
+        const float c = refn[0] * nrm[0] + refn[1] * nrm[1] + refn[2] * nrm[2];
+        nb.pass = !((double)depth_error > p.max_depth_error) && !(col_diff * col_diff + row_diff * row_diff > p.max_sq_reproj) &&
+                  !(c < p.min_cos_normal);
+      }
+    }
+  }
+  return nb;
+}
+
+// The conflict cut. `old` is what the mark of the turn `rank` replaced (atomicMax's return value): a mark of another turn
+// of this pass means the later of the two turns must not commit.
+__device__ __forceinline__ void cut_on_conflict(const Params& p, unsigned long long old, unsigned rank) {
+  if ((unsigned)(old >> 32) == p.epoch) {
+    const unsigned other = mark_rank(old);
+    if (other != rank) atomicMin(&p.ctl->rstar[p.slot], other > rank ? other : rank);
+  }
+}
+
+// What a wave has recorded in this pass: pixels, walks; turns walked and pixels absorbed (statistics).
+struct WaveLog { int rec_n, n_walks; unsigned long long walks, nodes; };
+// A turn of pool thread t (wave-uniform): its tick and rank = tau * T + t, its start pixel in the image being fused and
+// that pixel's depth.
+struct Turn { unsigned tau, rank; int seed; float depth; };
+// A walk whose first batch -- the start pixel alone -- has been taken already (seed_group): the pixel is marked and is the
+// wave's next record, its `sp` surviving neighbours are on the stack, ref / refn are its point and normal.
+struct Resume { int sp; float ref[3], refn[3]; };
+
+// the walk record: walk `wi` of pool thread t is the turn of tick tau, its pixels are records [first, first + count)
+__device__ __forceinline__ void put_walk(const Params& p, unsigned t, int wi, unsigned tau, int first, int count) {
+  p.w_tau[(size_t)t * p.window_cap + wi] = tau;
+  p.w_first[(size_t)t * p.window_cap + wi] = (unsigned)first;
+  p.w_count[(size_t)t * p.window_cap + wi] = (unsigned)count;
+}
+
+// The end of a walk that recorded [first, n). ok: it becomes the wave's next walk. Abandoned (record buffer or stack
+// spill full): nothing of it is recorded and the pass is cut at this turn.
+__device__ __forceinline__ bool end_walk(const Params& p, int lane, unsigned t, unsigned tau, unsigned rank, bool ok, int first, int n,
+                                         WaveLog* log) {
+  if (!ok) {
+    if (lane == 0) atomicMin(&p.ctl->rstar[p.slot], rank);
+    return false;
+  }
+  if (lane == 0) put_walk(p, t, log->n_walks, tau, first, n - first);
+  log->nodes += (unsigned long long)(n - first);
+  log->rec_n = n;
+  log->n_walks += 1;
+  return true;
+}
+
 // One turn of pool thread t: StereoFusion::Fuse's traversal (fusion.cc:401-489) from `seed` (free for t, positive
 // depth), executed by the 64 lanes of the wave together (every variable that steers the control flow is wave-uniform).
-// rec_n: pixels the wave has recorded in this pass; n_walks: its walks. false: record buffer or stack spill full --
-// the turn is abandoned and cuts the pass at its own rank.
+// false: record buffer or stack spill full -- the turn is abandoned and cuts the pass at its own rank (end_walk).
 //
 // The time of a walk is a chain of dependent memory round trips per absorbed pixel, so the chain is kept short:
 //  * the mark (atomicMax) is issued first and its return value looked at LAST, after the neighbour loads of the
@@ -253,45 +374,41 @@ __device__ inline void note_window_pixel(const Params& p, const WaveStack& st, u
 //    was tested a moment ago and the only mark made since is that of the pixel being expanded, which is another pixel;
 //    its depth travels in the stack entry. Older entries are looked at again when they surface (the walk may have
 //    absorbed them by another path).
-__device__ __forceinline__ bool walk_turn(const Params& p, const WalkTables& tb, const WaveStack& st, int lane, unsigned t, unsigned tau,
-                          unsigned win_tau0, unsigned rank, int seed, float seed_depth, int* rec_n, int* n_walks, unsigned long long* stat_nodes) {
-  const unsigned long long key = ((unsigned long long)p.epoch << 32) | (unsigned long long)(0xFFFFFFFFu - rank);
+__device__ __forceinline__ bool walk_turn(const Params& p, const WalkTables& tb, const WaveStack& st, int lane, unsigned t, unsigned win_tau0,
+                                          const Turn& turn, WaveLog* log) {
+  const unsigned rank = turn.rank;
+  const unsigned long long key = mark_key(p.epoch, rank);
   unsigned* const rec_pix = p.rec_pix + (size_t)t * kRecordBuf;
   unsigned* const rec_meta = p.rec_meta + (size_t)t * kRecordBuf;
-  const int first = *rec_n;
+  const int first = log->rec_n;
   int n = first, recorded = 0, nin = 0, sp = 0;
   float ref[3] = {0.f, 0.f, 0.f}, refn[3] = {0.f, 0.f, 0.f};
-  int img = p.image, pix = seed, level = 0;
-  unsigned long long goff = (unsigned long long)tb.images[p.image].pix_off + (unsigned long long)seed;
-  float depth = seed_depth;
+  int img = p.image, pix = turn.seed, level = 0;
+  unsigned long long goff = (unsigned long long)tb.images[p.image].pix_off + (unsigned long long)turn.seed;
+  float depth = turn.depth;
   bool ok = true;
   for (;;) {
     // ---- absorb (img, pix, level): fusion.cc:437-472 ----
     const DevImage& im = tb.images[img];
-    const int row = pix / im.dw, col = pix - row * im.dw;
-    const float hx = (float)col * depth, hy = (float)row * depth;
     float xyz[3];
-    for (int r = 0; r < 3; ++r)
-      xyz[r] = im.inv_P[4 * r] * hx + im.inv_P[4 * r + 1] * hy + im.inv_P[4 * r + 2] * depth + im.inv_P[4 * r + 3] * 1.0f;
-    const bool in_box = !(xyz[0] < p.bmin[0] || xyz[1] < p.bmin[1] || xyz[2] < p.bmin[2] || xyz[0] > p.bmax[0] ||
-                          xyz[1] > p.bmax[1] || xyz[2] > p.bmax[2]);
+    back_project(im, pix, depth, xyz);
+    const bool inb = in_box(p, xyz);
     if (recorded >= p.rec_cap) break;  // record capacity of one walk: the walk ends
     if (n >= kRecordBuf) { ok = false; break; }
     unsigned long long old = 0ull;
     if (lane == 0) {
       rec_pix[n] = (unsigned)pix;
-      rec_meta[n] = (unsigned)img | (in_box ? 0x80000000u : 0u);
+      rec_meta[n] = (unsigned)img | (inb ? 0x80000000u : 0u);
       old = atomicMax(p.word + goff, key);  // (looked at below, after the neighbour loads have been issued)
       note_window_pixel(p, st, t, win_tau0, img, pix);
     }
     ++n; ++recorded;
     bool expand = false, capped = false;
-    if (in_box) {
+    if (inb) {
       ++nin;
       if (level == 0) {
         const float* nl = p.normal + 3 * goff;
-        const float nl0 = nl[0], nl1 = nl[1], nl2 = nl[2];
-        for (int r = 0; r < 3; ++r) refn[r] = im.inv_R[3 * r] * nl0 + im.inv_R[3 * r + 1] * nl1 + im.inv_R[3 * r + 2] * nl2;
+        rotate_normal(im, nl[0], nl[1], nl[2], refn);
         ref[0] = xyz[0]; ref[1] = xyz[1]; ref[2] = xyz[2];
       }
       capped = nin >= p.elem_cap;  // max_num_pixels reached (fusion.cc:470-472): the walk ends after the mark is settled
@@ -304,57 +421,20 @@ __device__ __forceinline__ bool walk_turn(const Params& p, const WalkTables& tb,
       const int o0 = tb.optr[img], nov = tb.optr[img + 1] - o0;
       for (int base = 0; base < nov; base += kWave) {
         const int k = base + lane;
-        bool pass = false;
-        unsigned long long qoff = 0ull;
-        int q = 0, next = 0;
-        float d = 0.0f;
-        if (k < nov) {
-          next = tb.oidx[o0 + k];
-          const DevImage& nx = tb.images[next];
-          if (nx.pos >= p.step) {  // used, and not fused in an earlier step
-            float np[3];
-            for (int r = 0; r < 3; ++r) np[r] = nx.P[4 * r] * xyz[0] + nx.P[4 * r + 1] * xyz[1] + nx.P[4 * r + 2] * xyz[2] + nx.P[4 * r + 3];
-            const float fcol = roundf(np[0] / np[2]), frow = roundf(np[1] / np[2]);
-            if (fcol >= 0.0f && frow >= 0.0f && fcol < (float)nx.dw && frow < (float)nx.dh) {
-              const int qcol = (int)fcol, qrow = (int)frow;
-              q = qrow * nx.dw + qcol;
-              qoff = (unsigned long long)nx.pix_off + (unsigned long long)q;
-              const unsigned long long w = ld_word(p.word + qoff);
-              d = p.depth[qoff];
-              const float* nl = p.normal + 3 * qoff;
-              const float nl0 = nl[0], nl1 = nl[1], nl2 = nl[2];
-              // (qoff != goff: the pixel being expanded -- an image listed as its own neighbour -- is masked by the
-              // mark issued a moment ago, which this load is not ordered behind)
-              if (qoff != goff && !masked_for(w, p.epoch, (unsigned)p.T, t) && !(d <= 0.0f)) {
-                float proj[3];
-                for (int r = 0; r < 3; ++r)
-                  proj[r] = nx.P[4 * r] * ref[0] + nx.P[4 * r + 1] * ref[1] + nx.P[4 * r + 2] * ref[2] + nx.P[4 * r + 3] * 1.0f;
-                const float depth_error = fabsf((proj[2] - d) / d);
-                const float col_diff = proj[0] / proj[2] - (float)qcol;
-                const float row_diff = proj[1] / proj[2] - (float)qrow;
-                float nrm[3];
-                for (int r = 0; r < 3; ++r) nrm[r] = nx.inv_R[3 * r] * nl0 + nx.inv_R[3 * r + 1] * nl1 + nx.inv_R[3 * r + 2] * nl2;
-                const float c = refn[0] * nrm[0] + refn[1] * nrm[1] + refn[2] * nrm[2];
-                pass = !((double)depth_error > p.max_depth_error) && !(col_diff * col_diff + row_diff * row_diff > p.max_sq_reproj) &&
-                       !(c < p.min_cos_normal);
-              }
-            }
-          }
-        }
-        const unsigned long long m = __ballot(pass);
+        Neighbour nb{};
+        if (k < nov) nb = test_neighbour(p, tb, t, tb.oidx[o0 + k], goff, xyz, ref, refn);
+        const unsigned long long m = __ballot(nb.pass);
         const int cnt = __popcll(m);
         if (sp + cnt > kStackLds + p.spill_cap) { ok = false; break; }
-        if (pass) st.put(sp + __popcll(m & ((1ull << lane) - 1ull)), qoff, make_uint2((unsigned)q, (unsigned)next | ((unsigned)(level + 1) << 16)), d);
+        if (nb.pass) st.put(sp + lane_pos(m, lane), nb.qoff, make_uint2((unsigned)nb.q, (unsigned)nb.next | ((unsigned)(level + 1) << 16)), nb.d);
         sp += cnt;
         pushed += cnt;
       }
     }
-    // ---- the mark's old value: a mark of another turn of this pass means the later of the two turns must not commit ----
+    // ---- the mark's old value. Lane 0 made the mark; the shuffle is also where the other lanes wait for it: the words
+    // they read when they pop (below) must show this pixel as masked ----
     old = shfl64(old, 0);
-    if ((unsigned)(old >> 32) == p.epoch) {
-      const unsigned other = 0xFFFFFFFFu - (unsigned)old;
-      if (other != rank && lane == 0) atomicMin(&p.ctl->rstar[p.slot], other > rank ? other : rank);
-    }
+    if (lane == 0) cut_on_conflict(p, old, rank);
     if (!ok) {
       if (lane == 0) atomicOr(&p.ctl->flags, 1u);
       break;
@@ -402,20 +482,7 @@ __device__ __forceinline__ bool walk_turn(const Params& p, const WalkTables& tb,
     if (!found) break;
     goff = uniform(goff); pix = uniform(pix); img = uniform(img); level = uniform(level); depth = uniform(depth);
   }
-  if (!ok) {  // abandoned: nothing of it is recorded, the pass is cut at this turn
-    if (lane == 0) atomicMin(&p.ctl->rstar[p.slot], rank);
-    return false;
-  }
-  if (lane == 0) {
-    const int wi = *n_walks;
-    p.w_tau[(size_t)t * p.window_cap + wi] = tau;
-    p.w_first[(size_t)t * p.window_cap + wi] = (unsigned)first;
-    p.w_count[(size_t)t * p.window_cap + wi] = (unsigned)(n - first);
-  }
-  *stat_nodes += (unsigned long long)(n - first);
-  *rec_n = n;
-  *n_walks += 1;
-  return true;
+  return end_walk(p, lane, t, turn.tau, rank, ok, first, n, log);
 }
 
 // The same turn with the frontier expanded SEVERAL ENTRIES AT A TIME (round 6). walk_turn is a chain of one memory
@@ -433,25 +500,25 @@ __device__ __forceinline__ bool walk_turn(const Params& p, const WalkTables& tb,
 // turn has replaced since stays, and whoever looked at the word in between has at worst recorded a conflict that cuts
 // the pass early -- never a wrong mask) and the turn is repeated by walk_turn: return value 2. An entry that was absorbed
 // by another path since it was pushed -- or twice in one batch -- is recognised by the old value of its own mark.
-__device__ __forceinline__ int walk_turn_wide(const Params& p, const WalkTables& tb, const WaveStack& st, int lane, unsigned t, unsigned tau,
-                               unsigned win_tau0, unsigned rank, int seed, float seed_depth, int* rec_n, int* n_walks, unsigned long long* stat_nodes,
-                               int resume_sp = -1, const float* resume_ref = nullptr, const float* resume_refn = nullptr) {
-  const unsigned long long key = ((unsigned long long)p.epoch << 32) | (unsigned long long)(0xFFFFFFFFu - rank);
+__device__ __forceinline__ int walk_turn_wide(const Params& p, const WalkTables& tb, const WaveStack& st, int lane, unsigned t, unsigned win_tau0,
+                                              const Turn& turn, WaveLog* log, const Resume* resume) {
+  const unsigned rank = turn.rank;
+  const unsigned long long key = mark_key(p.epoch, rank);
   unsigned* const rec_pix = p.rec_pix + (size_t)t * kRecordBuf;
   unsigned* const rec_meta = p.rec_meta + (size_t)t * kRecordBuf;
-  const int first = *rec_n;
+  const int first = log->rec_n;
   const int G = p.wide_group, NBF = kWave / G;
   const int u_wide = lane / G, k_wide = lane - u_wide * G;
   int n = first, sp = 1;
   float ref[3] = {0.f, 0.f, 0.f}, refn[3] = {0.f, 0.f, 0.f};
-  if (resume_sp >= 0) {
+  if (resume) {
     // the seed's batch has been taken already (seed_group): the seed is marked and recorded at `first`, its surviving
     // neighbours are on the stack, the reference point and normal come with the call
     n = first + 1;
-    sp = resume_sp;
-    for (int r = 0; r < 3; ++r) { ref[r] = resume_ref[r]; refn[r] = resume_refn[r]; }
+    sp = resume->sp;
+    for (int r = 0; r < 3; ++r) { ref[r] = resume->ref[r]; refn[r] = resume->refn[r]; }
   } else if (lane == 0) {
-    st.put(0, (unsigned long long)tb.images[p.image].pix_off + (unsigned long long)seed, make_uint2((unsigned)seed, (unsigned)p.image), seed_depth);
+    st.put(0, (unsigned long long)tb.images[p.image].pix_off + (unsigned long long)turn.seed, make_uint2((unsigned)turn.seed, (unsigned)p.image), turn.depth);
   }
   __syncthreads();
   bool ok = true, narrow = false;
@@ -473,89 +540,48 @@ __device__ __forceinline__ int walk_turn_wide(const Params& p, const WalkTables&
     unsigned long long old = 0ull;
     if (have && k == 0) old = atomicMax(p.word + goff, key);  // (looked at below, after the neighbour loads have been issued)
     const DevImage& im = tb.images[img];
-    const int row = pix / im.dw, col = pix - row * im.dw;
-    const float hx = (float)col * depth, hy = (float)row * depth;
     float xyz[3];
-    for (int r = 0; r < 3; ++r)
-      xyz[r] = im.inv_P[4 * r] * hx + im.inv_P[4 * r + 1] * hy + im.inv_P[4 * r + 2] * depth + im.inv_P[4 * r + 3] * 1.0f;
-    const bool in_box = !(xyz[0] < p.bmin[0] || xyz[1] < p.bmin[1] || xyz[2] < p.bmin[2] || xyz[0] > p.bmax[0] ||
-                          xyz[1] > p.bmax[1] || xyz[2] > p.bmax[2]);
+    back_project(im, pix, depth, xyz);
+    const bool inb = in_box(p, xyz);
     if (first_batch) {  // the seed: the walk's reference point and normal, for every lane
       const float* nl = p.normal + 3 * goff;
-      const float nl0 = nl[0], nl1 = nl[1], nl2 = nl[2];
-      for (int r = 0; r < 3; ++r) refn[r] = im.inv_R[3 * r] * nl0 + im.inv_R[3 * r + 1] * nl1 + im.inv_R[3 * r + 2] * nl2;
+      rotate_normal(im, nl[0], nl[1], nl[2], refn);
       for (int r = 0; r < 3; ++r) ref[r] = xyz[r];
     }
-    // ---- neighbour k of entry u (fusion.cc:474-488 and the mask-independent tests of :407-447) ----
-    bool pass = false;
-    unsigned long long qoff = 0ull;
-    int q = 0, next = 0;
-    float d = 0.0f;
-    if (have && in_box && level < p.max_level) {
+    // ---- neighbour k of entry u ----
+    Neighbour nb{};
+    if (have && inb && level < p.max_level) {
       const int o0 = tb.optr[img], nov = tb.optr[img + 1] - o0;
-      if (k < nov) {
-        next = tb.oidx[o0 + k];
-        const DevImage& nx = tb.images[next];
-        if (nx.pos >= p.step) {  // used, and not fused in an earlier step
-          float np[3];
-          for (int r = 0; r < 3; ++r) np[r] = nx.P[4 * r] * xyz[0] + nx.P[4 * r + 1] * xyz[1] + nx.P[4 * r + 2] * xyz[2] + nx.P[4 * r + 3];
-          const float fcol = roundf(np[0] / np[2]), frow = roundf(np[1] / np[2]);
-          if (fcol >= 0.0f && frow >= 0.0f && fcol < (float)nx.dw && frow < (float)nx.dh) {
-            const int qcol = (int)fcol, qrow = (int)frow;
-            q = qrow * nx.dw + qcol;
-            qoff = (unsigned long long)nx.pix_off + (unsigned long long)q;
-            const unsigned long long w = ld_word(p.word + qoff);
-            d = p.depth[qoff];
-            const float* nl = p.normal + 3 * qoff;
-            const float nl0 = nl[0], nl1 = nl[1], nl2 = nl[2];
-            if (qoff != goff && !masked_for(w, p.epoch, (unsigned)p.T, t) && !(d <= 0.0f)) {
-              float proj[3];
-              for (int r = 0; r < 3; ++r)
-                proj[r] = nx.P[4 * r] * ref[0] + nx.P[4 * r + 1] * ref[1] + nx.P[4 * r + 2] * ref[2] + nx.P[4 * r + 3] * 1.0f;
-              const float depth_error = fabsf((proj[2] - d) / d);
-              const float col_diff = proj[0] / proj[2] - (float)qcol;
-              const float row_diff = proj[1] / proj[2] - (float)qrow;
-              float nrm[3];
-              for (int r = 0; r < 3; ++r) nrm[r] = nx.inv_R[3 * r] * nl0 + nx.inv_R[3 * r + 1] * nl1 + nx.inv_R[3 * r + 2] * nl2;
-              const float c = refn[0] * nrm[0] + refn[1] * nrm[1] + refn[2] * nrm[2];
-              pass = !((double)depth_error > p.max_depth_error) && !(col_diff * col_diff + row_diff * row_diff > p.max_sq_reproj) &&
-                     !(c < p.min_cos_normal);
-            }
-          }
-        }
-      }
+      if (k < nov) nb = test_neighbour(p, tb, t, tb.oidx[o0 + k], goff, xyz, ref, refn);
     }
     // ---- the marks' old values: is the entry absorbed (free for this thread until now)? ----
     old = shfl64(old, (!first_batch && u * G < kWave) ? u * G : 0);
     const bool absorbed = have && !masked_for(old, p.epoch, (unsigned)p.T, t);
-    if (absorbed && k == 0 && (unsigned)(old >> 32) == p.epoch) {  // a mark of another turn of this pass: the later turn must not commit
-      const unsigned other = 0xFFFFFFFFu - (unsigned)old;
-      if (other != rank) atomicMin(&p.ctl->rstar[p.slot], other > rank ? other : rank);
-    }
+    if (absorbed && k == 0) cut_on_conflict(p, old, rank);
     {
       const unsigned long long ma = __ballot(absorbed && k == 0);
       if (absorbed && k == 0) {
         note_window_pixel(p, st, t, win_tau0, img, pix);
-        const int at = n + __popcll(ma & ((1ull << lane) - 1ull));
+        const int at = n + lane_pos(ma, lane);
         rec_pix[at] = (unsigned)pix;
-        rec_meta[at] = (unsigned)img | (in_box ? 0x80000000u : 0u);
+        rec_meta[at] = (unsigned)img | (inb ? 0x80000000u : 0u);
       }
       n += __popcll(ma);
     }
     // ---- push the survivors of the absorbed entries ----
-    pass = pass && absorbed;
+    bool pass = nb.pass && absorbed;
     {
       // The same pixel is usually a neighbour of several entries of the batch (every absorbed pixel of image A projects
       // near the same pixel of image B): pushed once per parent it would come back as that many stack entries, all but
       // one of them dead. One survivor per pixel: the lane that holds the pixel's hash slot (lanes whose slot is held by
       // another pixel all stay: harmless).
-      const int hs = (int)((qoff * 0x9E3779B97F4A7C15ull) >> 57);  // 7 bits
-      st.cand[lane] = pass ? qoff : ~0ull;
+      const int hs = (int)((nb.qoff * 0x9E3779B97F4A7C15ull) >> 57);  // 7 bits
+      st.cand[lane] = pass ? nb.qoff : ~0ull;
       if (pass) st.slot[hs] = lane;
       __syncthreads();
       if (pass) {
         const int holder = st.slot[hs];
-        if (holder != lane && st.cand[holder] == qoff) pass = false;
+        if (holder != lane && st.cand[holder] == nb.qoff) pass = false;
       }
     }
     const unsigned long long m = __ballot(pass);
@@ -566,7 +592,7 @@ __device__ __forceinline__ int walk_turn_wide(const Params& p, const WalkTables&
       ok = false;
       break;
     }
-    if (pass) st.put(base + __popcll(m & ((1ull << lane) - 1ull)), qoff, make_uint2((unsigned)q, (unsigned)next | ((unsigned)(level + 1) << 16)), d);
+    if (pass) st.put(base + lane_pos(m, lane), nb.qoff, make_uint2((unsigned)nb.q, (unsigned)nb.next | ((unsigned)(level + 1) << 16)), nb.d);
     sp = base + cnt;
     __syncthreads();  // the pushes (LDS / spill) before the pops of the next batch
   }
@@ -581,19 +607,114 @@ __device__ __forceinline__ int walk_turn_wide(const Params& p, const WalkTables&
     __syncthreads();
     return 2;
   }
-  if (!ok) {  // abandoned: nothing of it is recorded, the pass is cut at this turn
-    if (lane == 0) atomicMin(&p.ctl->rstar[p.slot], rank);
-    return 0;
+  return end_walk(p, lane, t, turn.tau, rank, ok, first, n, log) ? 1 : 0;
+}
+
+// One turn, from the reset of the window's note to its use: breadth-first where that is allowed (`resume`: from where
+// seed_group left it), depth-first where it is not or where the breadth-first walk met the limits of the traversal and
+// took its marks back (2); then the start pixels of this window the walk absorbed leave *m: they are no longer free for
+// this thread. false: the turn was abandoned.
+__device__ __forceinline__ bool take_turn(const Params& p, const WalkTables& tb, const WaveStack& st, int lane, unsigned t, unsigned win_tau0,
+                                          const Turn& turn, WaveLog* log, const Resume* resume, unsigned long long* m) {
+  if (lane == 0) *st.win = 0ull;
+  __syncthreads();
+  int done = p.wide_group > 0 ? walk_turn_wide(p, tb, st, lane, t, win_tau0, turn, log, resume) : 2;
+  if (done == 2) {
+    if (lane == 0) *st.win = 0ull;  // (the repeated walk notes its own pixels)
+    __syncthreads();
+    done = walk_turn(p, tb, st, lane, t, win_tau0, turn, log) ? 1 : 0;
   }
-  if (lane == 0) {
-    const int wi = *n_walks;
-    p.w_tau[(size_t)t * p.window_cap + wi] = tau;
-    p.w_first[(size_t)t * p.window_cap + wi] = (unsigned)first;
-    p.w_count[(size_t)t * p.window_cap + wi] = (unsigned)(n - first);
+  if (!done) return false;
+  __syncthreads();
+  *m &= ~*st.win;
+  __syncthreads();
+  return true;
+}
+
+// Several start pixels at once: the first batch of up to 64 / wide_group consecutive turns of the window m (s, d: every
+// lane's start pixel and its depth) taken together, lane (u, k) = (start pixel, neighbour). Worthwhile when the thread
+// has a run of turns whose walks absorb nothing but their start pixel (stripes the other images do not see: ten times
+// the turns of an ordinary stripe, and a pass lasts as long as its slowest wave). The turns before the first start pixel
+// with a surviving neighbour are complete and leave m; that one goes on as an ordinary walk: *turn and *resume, the
+// return value 1 (0: no such start pixel). -1: fewer than two turns of the window can still commit -- nothing was done.
+__device__ __forceinline__ int seed_group(const Params& p, const WalkTables& tb, const WaveStack& st, int lane, unsigned t, unsigned win_tau0,
+                                          unsigned rs, int s, float d, unsigned long long* m, WaveLog* log, Turn* turn, Resume* resume) {
+  const int G = p.wide_group, NBF = kWave / G;
+  const int u = lane / G, k = lane - u * G;
+  // the group: the lowest NBF candidates of the window whose ranks can still commit
+  int ng = 0, my_j = 0;
+  {
+    unsigned long long mm = *m;
+    for (int g = 0; g < NBF && mm != 0ull; ++g) {
+      const int jj = __ffsll((long long)mm) - 1;
+      mm &= mm - 1ull;
+      if ((win_tau0 + (unsigned)jj) * (unsigned)p.T + t >= rs) break;
+      if (u == g) my_j = jj;
+      ++ng;
+    }
   }
-  *stat_nodes += (unsigned long long)(n - first);
-  *rec_n = n;
-  *n_walks += 1;
+  if (ng < 2) return -1;
+  const bool have = u < ng;
+  const int seed_u = __shfl(s, my_j);
+  const float depth_u = __shfl(d, my_j);
+  const unsigned tau_u = win_tau0 + (unsigned)my_j;
+  const unsigned rank_u = tau_u * (unsigned)p.T + t;
+  const unsigned long long key_u = mark_key(p.epoch, rank_u);
+  const DevImage& im = tb.images[p.image];
+  const unsigned long long goff = (unsigned long long)im.pix_off + (unsigned long long)seed_u;
+  unsigned long long old = 0ull;
+  if (have && k == 0) old = atomicMax(p.word + goff, key_u);  // (looked at below, after the neighbour loads have been issued)
+  float xyz[3], refn[3];
+  back_project(im, seed_u, depth_u, xyz);
+  const bool inb = in_box(p, xyz);
+  {
+    const float* nl = p.normal + 3 * goff;
+    rotate_normal(im, nl[0], nl[1], nl[2], refn);
+  }
+  // neighbour k of start pixel u, with this pixel as its walk's reference
+  Neighbour nb{};
+  if (have && inb && 0 < p.max_level) {
+    const int o0 = tb.optr[p.image], nov = tb.optr[p.image + 1] - o0;
+    if (k < nov) nb = test_neighbour(p, tb, t, tb.oidx[o0 + k], goff, xyz, xyz, refn);
+  }
+  if (have && k == 0) cut_on_conflict(p, old, rank_u);
+  // the first start pixel with a surviving neighbour: the turns before it are complete (they absorbed their
+  // start pixel and nothing else, which no other turn of the group can tell from the sequential run); it goes on
+  // as an ordinary walk; the turns behind it take their marks back and are looked at again after that walk
+  const unsigned long long pm = __ballot(nb.pass);
+  int ustar = ng;
+  for (int g = ng - 1; g >= 0; --g)
+    if ((pm >> (g * G)) & ((1ull << G) - 1ull)) ustar = g;
+  if (have && k == 0 && u > ustar) {
+    unsigned long long expect = key_u;
+    __hip_atomic_compare_exchange_strong(p.word + goff, &expect, 0ull, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  const int nrec = ustar < ng ? ustar + 1 : ng;
+  if (have && k == 0 && u < nrec) {
+    unsigned* const rp = p.rec_pix + (size_t)t * kRecordBuf;
+    unsigned* const rm = p.rec_meta + (size_t)t * kRecordBuf;
+    rp[log->rec_n + u] = (unsigned)seed_u;
+    rm[log->rec_n + u] = (unsigned)p.image | (inb ? 0x80000000u : 0u);
+    if (u < ustar) put_walk(p, t, log->n_walks + u, tau_u, log->rec_n + u, 1);
+  }
+  // the candidates that are settled leave the window: start pixels 0 .. min(ustar, ng - 1) of the group
+  for (int g = 0; g < nrec; ++g) *m &= *m - 1ull;
+  log->walks += (unsigned long long)nrec;
+  log->nodes += (unsigned long long)ustar;
+  log->rec_n += ustar;
+  log->n_walks += ustar;
+  if (ustar == ng) return 0;
+  // ---- start pixel ustar goes on: its survivors onto the stack, its point and normal to every lane ----
+  const int src = ustar * G;
+  const bool mine = nb.pass && u == ustar;
+  const unsigned long long sm = __ballot(mine);
+  if (mine) st.put(lane_pos(sm, lane), nb.qoff, make_uint2((unsigned)nb.q, (unsigned)nb.next | (1u << 16)), nb.d);
+  resume->sp = __popcll(sm);
+  for (int r = 0; r < 3; ++r) { resume->ref[r] = __shfl(xyz[r], src); resume->refn[r] = __shfl(refn[r], src); }
+  turn->tau = uniform((unsigned)__shfl((int)tau_u, src));
+  turn->rank = turn->tau * (unsigned)p.T + t;
+  turn->seed = uniform(__shfl(seed_u, src));
+  turn->depth = uniform(__shfl(depth_u, src));
   return 1;
 }
 
@@ -627,8 +748,7 @@ __global__ void __launch_bounds__(kWave) fusion_walk_kernel(Params p) {
                p.spill_goff + (size_t)t * p.spill_cap, p.spill_pm + (size_t)t * p.spill_cap, p.spill_d + (size_t)t * p.spill_cap};
   const unsigned long long img_off = (unsigned long long)tb.images[p.image].pix_off;
   unsigned tau = p.tau0 + (t < p.rmod ? 1u : 0u);
-  int rec_n = 0, n_walks = 0;
-  unsigned long long walks = 0ull, nodes = 0ull;
+  WaveLog log{0, 0, 0ull, 0ull};
   bool stop = false;
   while (!stop && tau < p.tau_end) {
     // the next 64 turns of this thread: which start pixels are free (for this thread) and have a depth? Looked at once
@@ -652,179 +772,36 @@ __global__ void __launch_bounds__(kWave) fusion_walk_kernel(Params p) {
     const unsigned win_tau0 = tau;
     const unsigned next_tau = p.tau_end - tau > (unsigned)kWave ? tau + (unsigned)kWave : p.tau_end;
     while (m != 0ull) {
-      // ---- several start pixels at once (seed_group below): worthwhile when the thread has a run of turns whose walks
-      // absorb nothing but their start pixel (stripes the other images do not see: ten times the turns of an ordinary
-      // stripe, and a pass lasts as long as its slowest wave) ----
-      if (p.wide_group > 0 && (m & (m - 1ull)) != 0ull && rec_n + kWave <= kRecordBuf && n_walks + kWave <= p.window_cap) {
-        const int G = p.wide_group, NBF = kWave / G;
-        const int u = lane / G, k = lane - u * G;
-        // the group: the lowest NBF candidates of the window whose ranks can still commit
-        int ng = 0, my_j = 0;
-        {
-          unsigned long long mm = m;
-          for (int g = 0; g < NBF && mm != 0ull; ++g) {
-            const int jj = __ffsll((long long)mm) - 1;
-            mm &= mm - 1ull;
-            if ((win_tau0 + (unsigned)jj) * (unsigned)p.T + t >= rs) break;
-            if (u == g) my_j = jj;
-            ++ng;
-          }
-        }
-        if (ng >= 2) {
-          const bool have = u < ng;
-          const int seed_u = __shfl(s, my_j);
-          const float depth_u = __shfl(d, my_j);
-          const unsigned tau_u = win_tau0 + (unsigned)my_j;
-          const unsigned rank_u = tau_u * (unsigned)p.T + t;
-          const unsigned long long key_u = ((unsigned long long)p.epoch << 32) | (unsigned long long)(0xFFFFFFFFu - rank_u);
-          const unsigned long long goff = img_off + (unsigned long long)seed_u;
-          unsigned long long old = 0ull;
-          if (have && k == 0) old = atomicMax(p.word + goff, key_u);
-          const DevImage& im = tb.images[p.image];
-          const int row = seed_u / im.dw, col = seed_u - row * im.dw;
-          const float hx = (float)col * depth_u, hy = (float)row * depth_u;
-          float xyz[3], refn[3];
-          for (int r = 0; r < 3; ++r)
-            xyz[r] = im.inv_P[4 * r] * hx + im.inv_P[4 * r + 1] * hy + im.inv_P[4 * r + 2] * depth_u + im.inv_P[4 * r + 3] * 1.0f;
-          const bool in_box = !(xyz[0] < p.bmin[0] || xyz[1] < p.bmin[1] || xyz[2] < p.bmin[2] || xyz[0] > p.bmax[0] ||
-                                xyz[1] > p.bmax[1] || xyz[2] > p.bmax[2]);
-          {
-            const float* nl = p.normal + 3 * goff;
-            const float nl0 = nl[0], nl1 = nl[1], nl2 = nl[2];
-            for (int r = 0; r < 3; ++r) refn[r] = im.inv_R[3 * r] * nl0 + im.inv_R[3 * r + 1] * nl1 + im.inv_R[3 * r + 2] * nl2;
-          }
-          // neighbour k of start pixel u: the tests of walk_turn_wide with this pixel as the walk's reference
-          bool pass = false;
-          unsigned long long qoff = 0ull;
-          int q = 0, next = 0;
-          float qd = 0.0f;
-          if (have && in_box && 0 < p.max_level) {
-            const int o0 = tb.optr[p.image], nov = tb.optr[p.image + 1] - o0;
-            if (k < nov) {
-              next = tb.oidx[o0 + k];
-              const DevImage& nx = tb.images[next];
-              if (nx.pos >= p.step) {
-                float np[3];
-                for (int r = 0; r < 3; ++r) np[r] = nx.P[4 * r] * xyz[0] + nx.P[4 * r + 1] * xyz[1] + nx.P[4 * r + 2] * xyz[2] + nx.P[4 * r + 3];
-                const float fcol = roundf(np[0] / np[2]), frow = roundf(np[1] / np[2]);
-                if (fcol >= 0.0f && frow >= 0.0f && fcol < (float)nx.dw && frow < (float)nx.dh) {
-                  const int qcol = (int)fcol, qrow = (int)frow;
-                  q = qrow * nx.dw + qcol;
-                  qoff = (unsigned long long)nx.pix_off + (unsigned long long)q;
-                  const unsigned long long w = ld_word(p.word + qoff);
-                  qd = p.depth[qoff];
-                  const float* nl = p.normal + 3 * qoff;
-                  const float nl0 = nl[0], nl1 = nl[1], nl2 = nl[2];
-                  if (qoff != goff && !masked_for(w, p.epoch, (unsigned)p.T, t) && !(qd <= 0.0f)) {
-                    float proj[3];
-                    for (int r = 0; r < 3; ++r)
-                      proj[r] = nx.P[4 * r] * xyz[0] + nx.P[4 * r + 1] * xyz[1] + nx.P[4 * r + 2] * xyz[2] + nx.P[4 * r + 3] * 1.0f;
-                    const float depth_error = fabsf((proj[2] - qd) / qd);
-                    const float col_diff = proj[0] / proj[2] - (float)qcol;
-                    const float row_diff = proj[1] / proj[2] - (float)qrow;
-                    float nrm[3];
-                    for (int r = 0; r < 3; ++r) nrm[r] = nx.inv_R[3 * r] * nl0 + nx.inv_R[3 * r + 1] * nl1 + nx.inv_R[3 * r + 2] * nl2;
-                    const float c = refn[0] * nrm[0] + refn[1] * nrm[1] + refn[2] * nrm[2];
-                    pass = !((double)depth_error > p.max_depth_error) && !(col_diff * col_diff + row_diff * row_diff > p.max_sq_reproj) &&
-                           !(c < p.min_cos_normal);
-                  }
-                }
-              }
-            }
-          }
-          // marks of other turns of this pass under the start pixels: the later turn must not commit (as in the walks)
-          if (have && k == 0 && (unsigned)(old >> 32) == p.epoch) {
-            const unsigned other = 0xFFFFFFFFu - (unsigned)old;
-            if (other != rank_u) atomicMin(&p.ctl->rstar[p.slot], other > rank_u ? other : rank_u);
-          }
-          // the first start pixel with a surviving neighbour: the turns before it are complete (they absorbed their
-          // start pixel and nothing else, which no other turn of the group can tell from the sequential run); it goes on
-          // as an ordinary walk; the turns behind it take their marks back and are looked at again after that walk
-          const unsigned long long pm = __ballot(pass);
-          int ustar = ng;
-          for (int g = ng - 1; g >= 0; --g)
-            if ((pm >> (g * G)) & ((1ull << G) - 1ull)) ustar = g;
-          if (have && k == 0 && u > ustar) {
-            unsigned long long expect = key_u;
-            __hip_atomic_compare_exchange_strong(p.word + goff, &expect, 0ull, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          const int nrec = ustar < ng ? ustar + 1 : ng;
-          if (have && k == 0 && u < nrec) {
-            unsigned* const rp = p.rec_pix + (size_t)t * kRecordBuf;
-            unsigned* const rm = p.rec_meta + (size_t)t * kRecordBuf;
-            rp[rec_n + u] = (unsigned)seed_u;
-            rm[rec_n + u] = (unsigned)p.image | (in_box ? 0x80000000u : 0u);
-            if (u < ustar) {
-              p.w_tau[(size_t)t * p.window_cap + n_walks + u] = tau_u;
-              p.w_first[(size_t)t * p.window_cap + n_walks + u] = (unsigned)(rec_n + u);
-              p.w_count[(size_t)t * p.window_cap + n_walks + u] = 1u;
-            }
-          }
-          // the candidates that are settled leave the window: start pixels 0 .. min(ustar, ng - 1) of the group
-          {
-            unsigned long long mm = m;
-            for (int g = 0; g < nrec; ++g) mm &= mm - 1ull;
-            m = mm;
-          }
-          walks += (unsigned long long)nrec;
-          nodes += (unsigned long long)ustar;
-          rec_n += ustar;
-          n_walks += ustar;
-          if (ustar == ng) continue;
-          // ---- start pixel ustar goes on: its survivors onto the stack, its point and normal to every lane ----
-          const int src = ustar * G;
-          const bool mine = pass && u == ustar;
-          const unsigned long long sm = __ballot(mine);
-          if (mine) st.put(__popcll(sm & ((1ull << lane) - 1ull)), qoff, make_uint2((unsigned)q, (unsigned)next | (1u << 16)), qd);
-          float wref[3], wrefn[3];
-          for (int r = 0; r < 3; ++r) { wref[r] = __shfl(xyz[r], src); wrefn[r] = __shfl(refn[r], src); }
-          const unsigned tj = uniform((unsigned)__shfl((int)tau_u, src));
-          const unsigned rank = tj * (unsigned)p.T + t;
-          const int seed = uniform(__shfl(seed_u, src));
-          const float sd = uniform(__shfl(depth_u, src));
-          if (lane == 0) *st.win = 0ull;
-          __syncthreads();
-          int done = walk_turn_wide(p, tb, st, lane, t, tj, win_tau0, rank, seed, sd, &rec_n, &n_walks, &nodes, __popcll(sm), wref, wrefn);
-          if (done == 2) {
-            if (lane == 0) *st.win = 0ull;
-            __syncthreads();
-            done = walk_turn(p, tb, st, lane, t, tj, win_tau0, rank, seed, sd, &rec_n, &n_walks, &nodes) ? 1 : 0;
-          }
-          if (!done) { stop = true; break; }
-          __syncthreads();
-          m &= ~*st.win;
-          __syncthreads();
+      // ---- several start pixels at once, while their records and walks are sure to fit ----
+      if (p.wide_group > 0 && (m & (m - 1ull)) != 0ull && log.rec_n + kWave <= kRecordBuf && log.n_walks + kWave <= p.window_cap) {
+        Turn turn;
+        Resume resume;
+        const int went = seed_group(p, tb, st, lane, t, win_tau0, rs, s, d, &m, &log, &turn, &resume);
+        if (went == 0) continue;
+        if (went > 0) {
+          if (!take_turn(p, tb, st, lane, t, win_tau0, turn, &log, &resume, &m)) { stop = true; break; }
           continue;
         }
       }
+      // ---- the window's next start pixel alone ----
       const int j = __ffsll((long long)m) - 1;
       m &= m - 1ull;
-      const unsigned tj = win_tau0 + (unsigned)j;
-      const unsigned rank = tj * (unsigned)p.T + t;
-      if (rank >= rs) { stop = true; break; }
-      const int seed = uniform(__shfl(s, j));
-      const float sd = uniform(__shfl(d, j));
-      ++walks;
-      if (lane == 0) *st.win = 0ull;
-      __syncthreads();
-      int done = p.wide_group > 0 ? walk_turn_wide(p, tb, st, lane, t, tj, win_tau0, rank, seed, sd, &rec_n, &n_walks, &nodes) : 2;
-      if (done == 2) {
-        if (lane == 0) *st.win = 0ull;  // (the repeated walk notes its own pixels)
-        __syncthreads();
-        done = walk_turn(p, tb, st, lane, t, tj, win_tau0, rank, seed, sd, &rec_n, &n_walks, &nodes) ? 1 : 0;
-      }
-      if (!done) { stop = true; break; }
-      __syncthreads();
-      m &= ~*st.win;  // start pixels of this window the walk absorbed are no longer free for this thread
-      __syncthreads();
+      Turn turn;
+      turn.tau = win_tau0 + (unsigned)j;
+      turn.rank = turn.tau * (unsigned)p.T + t;
+      if (turn.rank >= rs) { stop = true; break; }
+      turn.seed = uniform(__shfl(s, j));
+      turn.depth = uniform(__shfl(d, j));
+      ++log.walks;
+      if (!take_turn(p, tb, st, lane, t, win_tau0, turn, &log, nullptr, &m)) { stop = true; break; }
     }
     if (!stop && (unsigned long long)next_tau * (unsigned)p.T + t >= (unsigned long long)rs) break;  // nothing from here on can commit in this pass
     tau = next_tau;
   }
   if (lane == 0) {
-    p.n_walks[t] = n_walks;
-    atomicAdd(&p.ctl->walks, walks);
-    atomicAdd(&p.ctl->nodes, nodes);
+    p.n_walks[t] = log.n_walks;
+    atomicAdd(&p.ctl->walks, log.walks);
+    atomicAdd(&p.ctl->nodes, log.nodes);
   }
 }
 
@@ -904,6 +881,17 @@ __device__ double wave_median(int m, Get get, float* s, int lane) {
   return (rc - idx) * (double)left + (idx - lf) * (double)right;
 }
 
+// The smallest image index above `last` among the m in-box pixels of a walk (`box`: their record indices), by the 64
+// lanes of a wave; 0x7FFFFFFF: none. From last = -1 on: the walk's distinct images, ascending.
+__device__ inline int next_image(const unsigned* rec_meta, const unsigned* box, int m, int last, int lane) {
+  int best = 0x7FFFFFFF;
+  for (int a = lane; a < m; a += kWave) {
+    const int ia = (int)(rec_meta[(int)box[a]] & 0xFFFFu);
+    if (ia > last && ia < best) best = ia;
+  }
+  return wave_min(best);
+}
+
 // A pass, second half: the turns of rank < rstar are final -- their pixels become committed and are fused
 // (fusion.cc:449-466, 491-523). Block t = pool thread t; first every recorded pixel gets its point, normal and
 // colour (nine float columns), then wave w fuses walks w, w + 4, ...
@@ -929,11 +917,12 @@ __global__ void __launch_bounds__(kWave * kCommitWaves) fusion_commit_kernel(Par
     const int row = pix / im.dw, col = pix - row * im.dw;
     const float depth = p.depth[goff];
     const float* nl = p.normal + 3 * goff;
-    const float nl0 = nl[0], nl1 = nl[1], nl2 = nl[2];
-    const float hx = (float)col * depth, hy = (float)row * depth;
+    float xyz[3], nrm[3];
+    rotate_normal(im, nl[0], nl[1], nl[2], nrm);
+    back_project(im, pix, depth, xyz);
     for (int r = 0; r < 3; ++r) {
-      vals[(size_t)r * kRecordBuf + e] = im.inv_P[4 * r] * hx + im.inv_P[4 * r + 1] * hy + im.inv_P[4 * r + 2] * depth + im.inv_P[4 * r + 3] * 1.0f;
-      vals[(size_t)(3 + r) * kRecordBuf + e] = im.inv_R[3 * r] * nl0 + im.inv_R[3 * r + 1] * nl1 + im.inv_R[3 * r + 2] * nl2;
+      vals[(size_t)r * kRecordBuf + e] = xyz[r];
+      vals[(size_t)(3 + r) * kRecordBuf + e] = nrm[r];
     }
     unsigned rgb = 0u;
     if (im.rgb) {  // nearest neighbour at the bitmap scale (bitmap.cc:329-334), colour 0 outside
@@ -964,8 +953,7 @@ __global__ void __launch_bounds__(kWave * kCommitWaves) fusion_commit_kernel(Par
         inb = (meta >> 31) != 0u;
       }
       const unsigned long long mk = __ballot(inb);
-      const int at = m + __popcll(mk & ((1ull << lane) - 1ull));
-      if (inb) box[at] = (unsigned)(first + e);
+      if (inb) box[m + lane_pos(mk, lane)] = (unsigned)(first + e);
       m += __popcll(mk);
     }
     if (m < p.min_num_pixels || m == 0) continue;
@@ -981,17 +969,7 @@ __global__ void __launch_bounds__(kWave * kCommitWaves) fusion_commit_kernel(Par
     if (norm < FLT_EPSILON) continue;
     // distinct images, ascending (the reference copies an unordered set)
     int nvis = 0;
-    for (int last = -1;;) {
-      int best = 0x7FFFFFFF;
-      for (int a = lane; a < m; a += kWave) {
-        const int ia = (int)(rec_meta[rec_of(a)] & 0xFFFFu);
-        if (ia > last && ia < best) best = ia;
-      }
-      best = wave_min(best);
-      if (best == 0x7FFFFFFF) break;
-      last = best;
-      ++nvis;
-    }
+    for (int last = -1; (last = next_image(rec_meta, box, m, last, lane)) != 0x7FFFFFFF;) ++nvis;
     unsigned long long off64 = 0ull;
     if (lane == 0) off64 = atomicAdd(&p.ctl->cursor, (unsigned long long)nvis);
     off64 = shfl64(off64, 0);
@@ -999,14 +977,8 @@ __global__ void __launch_bounds__(kWave * kCommitWaves) fusion_commit_kernel(Par
     const int off = fits ? (int)off64 : 0;
     int last = -1;
     for (int v = 0; v < nvis; ++v) {
-      int best = 0x7FFFFFFF;
-      for (int a = lane; a < m; a += kWave) {
-        const int ia = (int)(rec_meta[rec_of(a)] & 0xFFFFu);
-        if (ia > last && ia < best) best = ia;
-      }
-      best = wave_min(best);
-      if (fits && lane == 0) p.pool[off + v] = best;
-      last = best;
+      last = next_image(rec_meta, box, m, last, lane);
+      if (fits && lane == 0) p.pool[off + v] = last;
     }
     if (lane == 0) {
       const int seed = (int)rec_pix[first];  // a walk's first record is its start pixel
