@@ -345,8 +345,9 @@ struct pm_handle {
   DevBuf<uint32_t> src_fp_off;       // [S] the packed source images as slots of the problem's buffer resource
   const uint32_t* fp_base = nullptr; // its base (lowest address among them); null: the images lie too far apart
   const char* sweep_kernel = "";     // kernel of the last sweep launch (pm_get_sweep_kernel_name)
-  DevBuf<unsigned long long> evals;  // [3] last run: NCC evaluations of the sweep launches; of them answered without taps;
-                                     // evaluations of the initial cost answered without taps (PmParams::answered)
+  DevBuf<unsigned long long> evals;  // [4] last run: NCC evaluations of the sweep launches; of them answered without taps;
+                                     // evaluations of the initial cost answered without taps; sweep evaluations
+                                     // pruned (PmParams::answered)
   DevBuf<PmParams> plan;  // per-launch parameter blocks of the last (batched) run
   hipStream_t run_stream = nullptr;  // stream the last run was enqueued on
   PmParams base;
@@ -637,7 +638,7 @@ void Create(const pm_options& opt_in, const pm_problem& prob, pm_image_cache* ca
     h->mask.alloc((size_t)S * W * H);
     b.mask = h->mask.ptr;
   }
-  h->evals.alloc(3);
+  h->evals.alloc(4);
   b.evals = h->evals.ptr;
   b.answered = h->evals.ptr + 1;
   h->out_depth.alloc((size_t)W * H);
@@ -705,6 +706,10 @@ void RunBatchAsync(pm_handle** hs, int n, hipStream_t run_st = nullptr) {
   for (int b = 0; b < n; ++b) probs[b] = {&hs[b]->base, &hs[b]->tables, hs[b]->poses.ptr};
   std::vector<PmParams> host = pm_host::FillParamBlocks(sched, probs.data(), n, run_shape,
                                                         dev_switch_int("COLMAP_AMD_PM_XCD_MAP", 0), run_plan.fp_resource);
+  {  // COLMAP_AMD_PM_PRUNE (tests, A/B runs; read once per run): 0 = every listed evaluation runs (single-stage P4)
+    const int prune = dev_switch_int("COLMAP_AMD_PM_PRUNE", 1) != 0 ? 1 : 0;
+    for (PmParams& p : host) p.prune = prune;
+  }
 #ifdef COLMAP_AMD_DIAG_BUILD
   {  // diagnostics only (results are garbage): a fixed perturbation, to time a launch without far-flung random
      // hypotheses, and the ablations of the sweep kernels
@@ -731,7 +736,7 @@ void RunBatchAsync(pm_handle** hs, int n, hipStream_t run_st = nullptr) {
     if (h->mask.ptr) HIP_CALL(hipMemsetAsync(h->mask.ptr, 0, h->mask.count, st));
     if (h->prof.ptr)
       HIP_CALL(hipMemsetAsync(h->prof.ptr, 0, kPmProfSlots * sizeof(unsigned long long), st));
-    HIP_CALL(hipMemsetAsync(h->evals.ptr, 0, 3 * sizeof(unsigned long long), st));
+    HIP_CALL(hipMemsetAsync(h->evals.ptr, 0, 4 * sizeof(unsigned long long), st));
   }
   pm_launch_initial_cost(run_plan, h0->plan.ptr, n, st);
   for (int k = 0; k < limit; ++k) {
@@ -1231,6 +1236,15 @@ int pm_get_answered_count(pm_handle* h, unsigned long long* sweep_answered, unsi
     HIP_CALL(hipMemcpy(both, h->evals.ptr + 1, sizeof(both), hipMemcpyDeviceToHost));
     if (sweep_answered) *sweep_answered = both[0];
     if (initial_answered) *initial_answered = both[1];
+  });
+}
+
+int pm_get_pruned_count(pm_handle* h, unsigned long long* sweep_pruned) {
+  return Guard([&] {
+    PM_CHECK(h && h->ran, "pm_run must be called first");
+    HIP_CALL(hipSetDevice(h->device));
+    if (sweep_pruned)
+      HIP_CALL(hipMemcpy(sweep_pruned, h->evals.ptr + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost));
   });
 }
 

@@ -68,6 +68,8 @@ struct PmParams {
   int help;         // waves per column group of the 11 x 11 sweep kernel: 2 = a helper wave shares pass B (pm_sweep_pair_kernel, C = 1)
   int ablate;       // profiling only (COLMAP_AMD_PM_ABLATE): bit 0 skip the NCC task passes, bit 1 skip the
                     // hypothesis generation, bit 2 skip the backward-message pre-pass; results are garbage
+  int prune;        // 11 x 11 sweep kernels: 1 = P4 runs in two stages and skips the second-stage evaluations of hypotheses
+                    // that can no longer win (sweep_wave_body); 0 = single stage (COLMAP_AMD_PM_PRUNE=0). Same results
   int xcd_map;      // batched launch of the generic kernel: 0 problem = id % batch, 1 neighbouring problems per XCD
   float refK[4];    // rotated {fx, cx, fy, cy}
   float refInvK[4]; // rotated {1/fx, -cx/fx, 1/fy, -cy/fy}
@@ -99,8 +101,9 @@ struct PmParams {
   unsigned long long* prof; // optional phase-cycle counters [kPmProfSlots] (debug), else null
   unsigned long long* evals; // NCC evaluations executed by the sweep kernels of this run (one atomic
                              // add per workgroup at its end), always allocated
-  unsigned long long* answered; // [2] of them the 11 x 11 wave kernels answered without taps (pm_patch_class.h): by the
-                                // sweep kernels, by the initial cost; one atomic add per wave at its end
+  unsigned long long* answered; // [3] of them the 11 x 11 wave kernels answered without taps (pm_patch_class.h): by the
+                                // sweep kernels, by the initial cost; [2]: pruned by the sweep kernels (never listed for
+                                // stage 2 of P4); one atomic add per wave at its end
   unsigned long long* trace; // optional progress trace (debug, pm_enable_progress_trace): [column group][row / 128]
                              // device-wide clock when the group's wave reached that row, last sweep launch; else null
   int trace_stride;          // samples per column group

@@ -378,6 +378,13 @@ class PatchMatch:
         _check(lib().pm_get_answered_count(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def GetPrunedCount(self):
+        """Evaluations of the last run's sweep launches that the 11 x 11 kernels never ran because their hypothesis could
+        no longer win (partial cost sum above the current plane's complete one). GetEvaluationCount includes them."""
+        a = C.c_ulonglong()
+        _check(lib().pm_get_pruned_count(self._h, C.byref(a)))
+        return int(a.value)
+
     def EnablePhaseProfile(self, enable=True):
         _check(lib().pm_enable_phase_profile(self._h, 1 if enable else 0))
 
@@ -400,7 +407,10 @@ class PatchMatch:
 
     PHASE_NAMES = ("setup", "P0_tile", "P1_hypotheses", "P1w_patch_weights", "P2_priors", "P3a_cdf", "P3b_draws",
                    "P3c_tasks", "P4_homographies", "P4_tap_rounds", "P4_normalise", "P5a_sums", "P5b_argmin",
-                   "P5c_winner_tasks", "P6_homographies", "P6_tap_rounds", "P6_normalise", "P7_messages", "P8_rowend")
+                   "P5c_winner_tasks", "P6_homographies", "P6_tap_rounds", "P6_normalise", "P7_messages", "P8_rowend",
+                   # with the prune: P4_* above are stage 1 and P5a_sums the bound; then the list of stage 2, its batches,
+                   # and (with its normalisation) the finished sums
+                   "P4_stage2_list", "P4_stage2_homographies", "P4_stage2_tap_rounds", "P4_stage2_normalise_sums")
 
     def GetPhaseProfileSlots(self):
         """{phase: shader-clock cycles summed over the waves} of the profiled four-wave kernel + 'waves'."""

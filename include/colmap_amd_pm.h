@@ -174,6 +174,11 @@ int pm_get_evaluation_count(pm_handle* h, unsigned long long* sweep_evals, unsig
  * generic kernels): the patch lies wholly beside its source image, so its three window sums are +0, or the reference
  * patch is flat, so the cost is 2 whatever the sums. pm_get_evaluation_count keeps counting them. */
 int pm_get_answered_count(pm_handle* h, unsigned long long* sweep_answered, unsigned long long* initial_answered);
+/* Of those evaluations, the ones the 11 x 11 sweep kernels pruned (the last run; 0 for the generic kernels and with the
+ * development switch COLMAP_AMD_PM_PRUNE=0): evaluations of a hypothesis whose partial cost sum already exceeds the
+ * complete sum of the pixel's current plane, so it cannot be the argmin. pm_get_evaluation_count keeps counting them;
+ * a pruned task is never also counted as answered. */
+int pm_get_pruned_count(pm_handle* h, unsigned long long* sweep_pruned);
 /* Device pointers of the result maps in API layout (valid after pm_synchronize;
  * for consumers that stay on the GPU, e.g. the geometric pass). */
 int pm_get_device_maps(pm_handle* h, const float** depth, const float** normal);

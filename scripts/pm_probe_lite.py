@@ -111,6 +111,10 @@ def run(a):
             answered["initial_share"] = answered["initial_answered"] / max(answered["initial_evaluations"], 1)
             print(f"  answered without taps: sweeps {answered['sweep_share']:.4f} of the evaluations, "
                   f"initial cost {answered['initial_share']:.4f}", flush=True)
+            if hasattr(mvs.lib(), "pm_get_pruned_count"):
+                answered["sweep_pruned"] = sum(pm.GetPrunedCount() for pm in pms)
+                answered["pruned_share"] = answered["sweep_pruned"] / max(answered["sweep_evaluations"], 1)
+                print(f"  pruned: {answered['pruned_share']:.4f} of the sweeps' evaluations", flush=True)
         if a.profile:
             import json
             tot = {}
