@@ -686,9 +686,15 @@ void RunBatchAsync(pm_handle** hs, int n, hipStream_t run_st = nullptr) {
                                              : s.C,
                requested};
   }
-  const pm_host::RunShape run_shape =
-      pm_host::PlanRunShape(cols.data(), n, h0->base.ntaps, h0->W, h0->H, g_live_handles[h0->device & 15].load(),
-                            DeviceCUs(h0->device), cols_switch, dev_switch_int("COLMAP_AMD_PM_HELP", 0));
+  const int live = g_live_handles[h0->device & 15].load(), help_switch = dev_switch_int("COLMAP_AMD_PM_HELP", 0);
+  pm_host::RunShape run_shape = pm_host::PlanRunShape(cols.data(), n, h0->base.ntaps, h0->W, h0->H, live,
+                                                      DeviceCUs(h0->device), cols_switch, help_switch);
+  // ... and three columns per wave where that shape is the faster one (a full GPU, photometric, S <= 21)
+  const int narrow_C = run_shape.C;
+  run_shape = pm_host::PlanWideColumns(run_shape, cols.data(), n, h0->base.ntaps, h0->base.S, geom, h0->W, h0->H, live,
+                                       DeviceCUs(h0->device), cols_switch, help_switch,
+                                       dev_switch_int("COLMAP_AMD_PM_WIDE", 1),
+                                       PmRunPlan::wave_kernels_fit(h0->base, pm_host::kWideColumns, geom));
   // Which kernels the run launches, decided once. One kernel serves the whole batch: buffer-resource addressing only if
   // every problem's images allow it -- otherwise NO parameter block of the run carries a base.
   PmParams shape = h0->base;
@@ -748,7 +754,11 @@ void RunBatchAsync(pm_handle** hs, int n, hipStream_t run_st = nullptr) {
     HIP_CALL(hipEventRecord(h0->ev[2 * k], st));   // the events bracket the sweep kernel alone
     pm_launch_sweep(run_plan, sweep.rot, h0->plan.ptr + (size_t)(k + 1) * n, n, sweep.filter_photo, sweep.filter_geom,
                     st);
-    h0->sweep_kernel = run_plan.sweep_name;
+    // (a launch the library widened is a shape of its own: what was measured on the two-column launch, such as
+    // profiles/pm_sweep_traffic.json, does not describe it, so the run says which one it was)
+    h0->sweep_kernel = run_shape.C != narrow_C && run_plan.sweep == kPmQuad && run_plan.fp_resource
+                           ? "pm_sweep_quad_kernel (three columns)"
+                           : run_plan.sweep_name;
     HIP_CALL(hipEventRecord(h0->ev[2 * k + 1], st));
   }
   for (int b = 0; b < n; ++b) {

@@ -470,7 +470,8 @@ struct RunShape {
 };
 
 // Columns per wave by occupancy. A wave sweeps C columns top to bottom, so a launch has (problems x columns / C)
-// waves for 16 wave slots per CU. C = 2 is the fastest shape when the GPU is full (pm_pick_columns), but ONE
+// waves for 16 wave slots per CU. C = 2 is the shape a handle is created for (pm_pick_columns; a full GPU takes three,
+// PlanWideColumns below), but ONE
 // 2560 x 1920 problem -- how the reference's controller drives the seam, one problem per GPU thread
 // (mvs/patch_match.cc:190-204) -- then has 960 .. 1 280 waves for 4 096 slots: with fewer than ~3/4 of the slots
 // covered by everything alive on the device, one column per wave doubles the waves. The results do not depend
@@ -508,6 +509,41 @@ inline RunShape PlanRunShape(const HandleColumns* cols, int n, int ntaps, int W,
     run_help = 2;
   }
   return {run_C, run_help};
+}
+
+// ---- three columns per wave ----
+
+// The second step of the run shape, behind PlanRunShape: an AUTOMATIC two-column shape becomes three columns per wave
+// where the launch is issue-bound. A row step's phases outside the tap rounds cost the same instructions for two
+// columns as for three (at S = 20: 60 of 64 lanes in the lane-per-(column, view) phases, 24 stage-1 tasks = six whole
+// rounds, 15 cost sums), so a full GPU spends fewer instructions per column (measured in
+// DESIGN.md 1.5). Raised exactly when
+//   * the shape is PlanRunShape's own two columns: 11 x 11 window, no handle requested its columns, neither
+//     COLMAP_AMD_PM_COLS nor COLMAP_AMD_PM_HELP set, no helper wave;
+//   * the pass is photometric (the geometric block of three columns exceeds the workgroup's LDS budget) and the
+//     lane-per-(column, view) phases are still one pass: 3 S <= 64;
+//   * fits3: PmRunPlan::wave_kernels_fit at three columns -- a shape the wave kernels do not hold keeps two columns, it
+//     never reaches the generic family through this rule;
+//   * everything alive on the device, at three columns per wave, is at least kWideOversubscription times the 16 wave
+//     slots per CU the three-column kernel has: below that a launch is a few long waves per slot and its time is the
+//     longest wave's, which three columns lengthen. (2: measured at 2560 x 1920, S = 20 -- 8 images alive, 1.25 x the
+//     slots: three columns lose 1.4 %; 13 images, 2.03 x: they gain 2.2 %; the benchmark's 16, 2.5 x: 3.4 %.)
+// wide_switch: COLMAP_AMD_PM_WIDE -- 0 = never (the shape of PlanRunShape), 1 = the rule above, 2 = the rule without
+// its last clause (tests: images too small to fill a GPU).
+constexpr int kWideColumns = 3;
+constexpr int kWideOversubscription = 2;
+inline RunShape PlanWideColumns(RunShape shape, const HandleColumns* cols, int n, int ntaps, int S, bool geom, int W,
+                                int H, int live_handles, int ncu, int cols_switch, int help_switch, int wide_switch,
+                                bool fits3) {
+  bool automatic = ntaps == 121 && cols_switch <= 0 && help_switch <= 0 && wide_switch != 0;
+  for (int b = 0; b < n; ++b) automatic = automatic && !cols[b].requested;
+  if (!automatic || shape.C != 2 || shape.help != 1) return shape;
+  if (geom || kWideColumns * S > 64 || !fits3) return shape;
+  const long long slots = 16ll * ncu;
+  const int alive = std::max(n, live_handles);
+  const long long waves3 = (long long)alive * ((std::min(W, H) + kWideColumns - 1) / kWideColumns);
+  if (wide_switch != 2 && waves3 < kWideOversubscription * slots) return shape;
+  return {kWideColumns, 1};
 }
 
 // ---- sweep schedule ----

@@ -1600,8 +1600,9 @@ static_assert(kQuadThCap % 4 == 0 && kQuadThCap <= 64, "a batch is whole rounds 
 // profiles/r07_bench_ab_44_byte_record/.) Pass B pays for the one word with an AND and a shift per round.
 constexpr int kSlotWords = 10;
 // Columns per wave of the 11 x 11 wave kernels: the record's two column bits. (8 before the round records; a caller
-// that asks for 5..8 columns per group now gets the generic family, same bits. Two columns are the default and the
-// fastest shape -- 604 / 643 / 718 ms per launch at C = 2 / 3 / 4 -- so nothing that is fast is lost.)
+// that asks for 5..8 columns per group now gets the generic family, same bits. Nothing that is fast is lost: on a full
+// GPU three columns are the fastest shape since the prune -- bench 11.05 / 11.42 Mpix/s at C = 2 / 3, DESIGN.md 1.5;
+// four need two passes in the lane-per-(column, view) phases at S = 20 and were last measured slower than either.)
 constexpr int kWaveMaxColumns = 4;
 
 __device__ __forceinline__ uint32_t task16_pack(int c, int i, int s, int geom_only) {
@@ -2483,6 +2484,8 @@ template <bool GEOM, bool FILTER_PHOTO, bool FILTER_GEOM, bool MUBUF>
 __global__ void __launch_bounds__(64 * kQuadWaves, GEOM ? 4 : kQuadOcc) pm_sweep_quad_kernel(const PmParams* __restrict__ pp) {
   sweep_wave_body<GEOM, FILTER_PHOTO, FILTER_GEOM, kQuadWaves, kQuadThCap, MUBUF>(pp);
 }
+// (Runs of three columns per wave, pm_host::PlanWideColumns, use this kernel too, at the four workgroups per CU their
+// LDS block allows: DESIGN.md 1.5.)
 // Two waves per column group (sweep_wave_body, HELP = 2): launches that one wave per column cannot fill the GPU with.
 // Without the prune (kPairPrune): a row of ONE column is a serial chain of short phases on a half-empty GPU, and the
 // second pass A / publish / finish / sums of a two-stage P4 lengthen that chain by more than the rounds it drops
@@ -2591,8 +2594,9 @@ bool PmRunPlan::wave_kernels_fit(const PmParams& p, int C, bool geom) {
 
 int pm_pick_columns(int S, int ntaps, int num_samples, bool geom, int radius, int requested) {
   const size_t budget = 60 * 1024;
-  // default: 2 columns per wave of the 11 x 11 kernel (16 waves resident per CU, the lane-per-(column, view)
-  // phases are one pass; measured 604 / 643 / 718 ms per 16-image launch for C = 2 / 3 / 4), 4 for the generic kernel
+  // default: 2 columns per wave of the 11 x 11 kernel (what a handle allocates for and every launch that does not fill
+  // the GPU runs; a run that does takes three, pm_host::PlanWideColumns: bench 11.05 / 11.42 Mpix/s at C = 2 / 3),
+  // 4 for the generic kernel
   int c = requested > 0 ? requested : (ntaps == 121 ? 2 : 4);
   if (c > 64) c = 64;
   if (ntaps == 121 && requested <= 0) {
