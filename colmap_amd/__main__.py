@@ -18,6 +18,7 @@ COMMANDS = {
     "exhaustive_matcher": ("colmap_amd.exhaustive_matcher", "match the SIFT descriptors of all image pairs of a database (exe/feature.cc:120-143)"),
     "sequential_matcher": ("colmap_amd.sequential_matcher", "match every image with the next ones in name order (exe/feature.cc:270-297)"),
     "matches_importer": ("colmap_amd.matches_importer", "match the image pairs a text file lists (exe/feature.cc:226-268)"),
+    "geometric_verifier": ("colmap_amd.geometric_verifier", "estimate the two-view geometry of the matched pairs of a database (exe/feature.cc)"),
 }
 
 # matcher commands of the reference whose pairing is not built: named so that the message says what is missing

@@ -2,7 +2,8 @@
 (reference scene/database_sqlite.cc): image ids and names, SIFT descriptors, and the `matches` table. Pair ids and the
 blob layout follow util/types.h:209-239 and database_sqlite.cc:1365-1390: pair_id = 2147483647 * min(id) + max(id); the
 blob is uint32 [rows][2] in the order (smaller id's point, larger id's point); an empty result is rows = 0, cols = 2.
-`two_view_geometries` is only looked at, never written: that is the state `geometric_verifier` picks up.
+The matchers only look at `two_view_geometries`; `geometric_verifier` (colmap_amd/geometric_verifier.py) reads cameras,
+keypoints and matches and writes its rows.
 """
 from __future__ import annotations
 
@@ -157,3 +158,84 @@ class Database:
         if not self._has_table("two_view_geometries"):
             return 0
         return int(self.con.execute("SELECT COUNT(*) FROM two_view_geometries").fetchone()[0])
+
+    # -- what geometric verification reads and writes ---------------------------------------------------------------
+    def create_verification_tables(self):
+        """`cameras` and `keypoints` with the reference's column lists (database_sqlite.cc:2031-2038, 2101-2106), for
+        databases made here; a database made by `colmap` has them."""
+        self.con.executescript(
+            "CREATE TABLE IF NOT EXISTS cameras (camera_id INTEGER PRIMARY KEY AUTOINCREMENT NOT NULL, "
+            "model INTEGER NOT NULL, width INTEGER NOT NULL, height INTEGER NOT NULL, params BLOB, "
+            "prior_focal_length INTEGER NOT NULL);"
+            "CREATE TABLE IF NOT EXISTS keypoints (image_id INTEGER PRIMARY KEY NOT NULL, rows INTEGER NOT NULL, "
+            "cols INTEGER NOT NULL, data BLOB);")
+
+    def read_cameras(self) -> Dict[int, dict]:
+        """camera_id -> {model, width, height, params (float64), prior_focal_length} (database_sqlite.cc:2031-2038)."""
+        out = {}
+        for cid, model, width, height, params, prior in self.con.execute(
+                "SELECT camera_id, model, width, height, params, prior_focal_length FROM cameras ORDER BY camera_id"):
+            out[int(cid)] = {"model": int(model), "width": int(width), "height": int(height),
+                             "params": np.frombuffer(params or b"", np.float64).copy(), "prior_focal_length": bool(prior)}
+        return out
+
+    def read_image_camera_ids(self) -> Dict[int, int]:
+        return {int(i): int(c) for i, c in self.con.execute("SELECT image_id, camera_id FROM images ORDER BY image_id")}
+
+    def read_keypoints(self, image_id: int) -> np.ndarray:
+        """float32 [rows][cols], cols 2, 4 or 6, the first two are x, y (database_sqlite.cc:102-128); an image without
+        a row has none."""
+        if not self._has_table("keypoints"):
+            return np.zeros((0, 2), np.float32)
+        row = self.con.execute("SELECT rows, cols, data FROM keypoints WHERE image_id = ?", (image_id,)).fetchone()
+        if row is None or row[0] == 0:
+            return np.zeros((0, 2), np.float32)
+        rows, cols, data = row
+        if cols not in (2, 4, 6):
+            raise DatabaseError(f"image {image_id}: keypoints have {cols} columns, expected 2, 4 or 6")
+        if len(data or b"") != 4 * rows * cols:
+            raise DatabaseError(f"image {image_id}: keypoint blob has {len(data or b'')} bytes, expected {4 * rows * cols}")
+        return np.frombuffer(data, np.float32).reshape(rows, cols).copy()
+
+    def read_matched_pair_ids(self) -> List[int]:
+        """The pair ids of the `matches` table in pair-id order."""
+        return [int(r[0]) for r in self.con.execute("SELECT pair_id FROM matches ORDER BY pair_id")]
+
+    def exists_inlier_matches(self, image_id1: int, image_id2: int) -> bool:
+        """ExistsInlierMatches: a two_view_geometries row with inlier matches."""
+        if not self._has_table("two_view_geometries"):
+            return False
+        pid = image_pair_to_pair_id(image_id1, image_id2)
+        return self.con.execute("SELECT 1 FROM two_view_geometries WHERE pair_id = ? AND rows > 0", (pid,)).fetchone() is not None
+
+    def delete_two_view_geometry(self, image_id1: int, image_id2: int):
+        if self._has_table("two_view_geometries"):
+            self.con.execute("DELETE FROM two_view_geometries WHERE pair_id = ?", (image_pair_to_pair_id(image_id1, image_id2),))
+
+    def write_two_view_geometry(self, image_id1: int, image_id2: int, inlier_matches: np.ndarray, config: int,
+                                F: np.ndarray = None, H: np.ndarray = None):
+        """One row of `two_view_geometries`; the table is created with the reference's column list
+        (database_sqlite.cc:2144-2156) where it is absent, and only the columns an older table has are written.
+        inlier_matches: [n][2] as (point of image_id1, point of image_id2), stored in the order of the pair id, as the
+        matches blob. F and H are 9 row-major doubles; E, qvec, tvec, camera1 and camera2 stay NULL. A swapped pair
+        would need TwoViewGeometry::Invert; geometric verification works in pair-id order, so a geometry with F or H
+        is only accepted for image_id1 < image_id2."""
+        if not self._has_table("two_view_geometries"):
+            self.con.execute("CREATE TABLE IF NOT EXISTS two_view_geometries (pair_id INTEGER PRIMARY KEY NOT NULL, "
+                             "rows INTEGER NOT NULL, cols INTEGER NOT NULL, data BLOB, config INTEGER NOT NULL, F BLOB, "
+                             "E BLOB, H BLOB, qvec BLOB, tvec BLOB, camera1 BLOB, camera2 BLOB)")
+        m = np.asarray(inlier_matches, dtype=np.uint32).reshape(-1, 2)
+        if swap_image_pair(image_id1, image_id2):
+            if F is not None or H is not None:
+                raise DatabaseError("a two-view geometry with F or H must be written in the order of the pair id")
+            m = m[:, ::-1]
+        m = np.ascontiguousarray(m)
+
+        def blob(a):
+            return None if a is None else np.ascontiguousarray(a, np.float64).reshape(9).tobytes()
+        values = {"pair_id": image_pair_to_pair_id(image_id1, image_id2), "rows": m.shape[0], "cols": 2,
+                  "data": m.tobytes() if m.shape[0] else None, "config": int(config), "F": blob(F), "H": blob(H)}
+        have = self._columns("two_view_geometries")
+        cols = [c for c in values if c in have]
+        self.con.execute(f"INSERT INTO two_view_geometries ({', '.join(cols)}) VALUES ({', '.join('?' * len(cols))})",
+                         [values[c] for c in cols])

@@ -192,3 +192,22 @@ def match_sequential(database_path, matching_options=None, overlap=10, quadratic
     with database.Database(database_path) as db:
         blocks = fm.sequential_pair_blocks(fm.order_by_name(db.read_image_names()), overlap, quadratic_overlap)
         return fm.match_blocks(db, blocks, matching_options, gpu_index, cache_bytes, batch_pairs or fm.DEFAULT_BATCH_PAIRS)
+
+
+def verify_matches(database_path, options=None, gpu_index=0, batch_size=None):
+    """pycolmap.verify_matches (the geometric verification of controllers/feature_matching_utils.cc:595-662): estimates
+    the two-view geometry of every matched pair of the database on the GPU (needs an MI355X) and writes
+    `two_view_geometries`. options: a two_view_geometry.TwoViewGeometryOptions. Pairs on a route of
+    EstimateTwoViewGeometry that is not built (calibrated, shared focal, one-sided focal, spherical) are left without a
+    row and counted in the returned `not_built`."""
+    from . import database, geometric_verifier as gv
+    with database.Database(database_path) as db:
+        return gv.verify_matches(db, options, gpu_index, batch_size or gv.DEFAULT_BATCH_SIZE)
+
+
+def estimate_two_view_geometry(camera1, points1, camera2, points2, matches, options=None, stream_id=0, gpu_index=0):
+    """pycolmap.estimate_two_view_geometry (EstimateTwoViewGeometry, estimators/two_view_geometry.cc:552-640) on the
+    routes that need only a fundamental matrix and a homography. camera1 / camera2: two_view_geometry.CameraInfo;
+    points [.][2+]; matches uint32 [n][2]. Raises for a pair on a route that is not built."""
+    from . import two_view_geometry as tv
+    return tv.estimate_two_view_geometry(camera1, points1, camera2, points2, matches, options, stream_id, gpu_index)
