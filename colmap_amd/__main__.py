@@ -15,6 +15,7 @@ COMMANDS = {
     "model_comparer": ("colmap_amd.model_comparer", "align two sparse models and report per-image pose errors (exe/model.cc:520-631)"),
     "model_aligner": ("colmap_amd.model_aligner", "move a sparse model onto reference camera positions (exe/model.cc:257-424)"),
     "model_transformer": ("colmap_amd.model_transformer", "apply a stored similarity to a sparse model or a PLY (exe/model.cc:1081-1129)"),
+    "feature_extractor": ("colmap_amd.feature_extractor", "extract SIFT features of the images of a folder into a database (exe/feature.cc:58-118)"),
     "exhaustive_matcher": ("colmap_amd.exhaustive_matcher", "match the SIFT descriptors of all image pairs of a database (exe/feature.cc:120-143)"),
     "sequential_matcher": ("colmap_amd.sequential_matcher", "match every image with the next ones in name order (exe/feature.cc:270-297)"),
     "matches_importer": ("colmap_amd.matches_importer", "match the image pairs a text file lists (exe/feature.cc:226-268)"),
@@ -28,6 +29,11 @@ NOT_BUILT = {
     "transitive_matcher": "transitive pairing needs the graph of existing two-view geometries, which are never written here",
 }
 
+# other commands of the reference that are named so that the message says what is missing
+NOT_BUILT_OTHER = {
+    "feature_importer": "importing keypoints and descriptors from text files is missing; feature_extractor extracts them on the GPU",
+}
+
 
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -39,6 +45,9 @@ def main(argv=None) -> int:
     if argv[0] in NOT_BUILT:
         print(f"E Command `{argv[0]}` is not built: {NOT_BUILT[argv[0]]}. exhaustive_matcher, sequential_matcher and "
               "matches_importer --match_type pairs are.", file=sys.stderr)
+        return 1
+    if argv[0] in NOT_BUILT_OTHER:
+        print(f"E Command `{argv[0]}` is not built: {NOT_BUILT_OTHER[argv[0]]}.", file=sys.stderr)
         return 1
     if argv[0] not in COMMANDS:
         print(f"E Command `{argv[0]}` not recognized. To list the available commands, run `python -m colmap_amd help`.",

@@ -14,7 +14,8 @@ LIB_DIR = os.path.join(_ROOT, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libcolmap_amd.so")
 
 SOURCES = ["pm_api.cpp", "pm_kernels.hip", "ba_kernels.hip", "ba_schur_explicit.hip", "fusion.hip", "undistort.hip",
-           "obs_filter.hip", "model_stats.hip", "color_extract.hip", "model_align.hip", "feature_match.hip", "two_view.hip"]
+           "obs_filter.hip", "model_stats.hip", "color_extract.hip", "model_align.hip", "feature_match.hip", "two_view.hip",
+           "sift.hip"]
 
 # -ffp-contract=off: fused multiply-adds only where the source says fmaf(); the
 # arithmetic is specified operation by operation (oracle/pm_oracle.c header).

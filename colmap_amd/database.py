@@ -67,6 +67,7 @@ class Database:
             "rows INTEGER NOT NULL, cols INTEGER NOT NULL, data BLOB);"
             "CREATE TABLE IF NOT EXISTS matches (pair_id INTEGER PRIMARY KEY NOT NULL, rows INTEGER NOT NULL, "
             "cols INTEGER NOT NULL, data BLOB);")
+        self.create_verification_tables()   # cameras and keypoints: what feature extraction writes
         self._has_type = "type" in self._columns("descriptors")
 
     def close(self):
@@ -169,6 +170,32 @@ class Database:
             "prior_focal_length INTEGER NOT NULL);"
             "CREATE TABLE IF NOT EXISTS keypoints (image_id INTEGER PRIMARY KEY NOT NULL, rows INTEGER NOT NULL, "
             "cols INTEGER NOT NULL, data BLOB);")
+
+    # -- what feature extraction writes (controllers/feature_extraction.cc:238-300) ---------------------------------
+    def write_camera(self, model: int, width: int, height: int, params, prior_focal_length: bool = False,
+                     camera_id: int = None) -> int:
+        """Database::WriteCamera (database_sqlite.cc): params as float64; returns the camera id."""
+        blob = np.ascontiguousarray(params, np.float64).tobytes()
+        cur = self.con.execute("INSERT INTO cameras (camera_id, model, width, height, params, prior_focal_length) "
+                               "VALUES (?, ?, ?, ?, ?, ?)", (camera_id, int(model), int(width), int(height), blob,
+                                                             int(bool(prior_focal_length))))
+        return int(cur.lastrowid)
+
+    def write_keypoints(self, image_id: int, keypoints: np.ndarray):
+        """Database::WriteKeypoints: float32 [rows][6] = x, y, a11, a12, a21, a22 (or 2 / 4 columns), the form
+        read_keypoints reads."""
+        k = np.ascontiguousarray(keypoints, dtype=np.float32)
+        if k.ndim != 2 or k.shape[1] not in (2, 4, 6):
+            raise DatabaseError(f"image {image_id}: keypoints must be [rows][2, 4 or 6], got {k.shape}")
+        self.con.execute("INSERT INTO keypoints (image_id, rows, cols, data) VALUES (?, ?, ?, ?)",
+                         (image_id, k.shape[0], k.shape[1], k.tobytes()))
+
+    def exists_keypoints(self, image_id: int) -> bool:
+        return self._has_table("keypoints") and \
+            self.con.execute("SELECT 1 FROM keypoints WHERE image_id = ?", (image_id,)).fetchone() is not None
+
+    def exists_descriptors(self, image_id: int) -> bool:
+        return self.con.execute("SELECT 1 FROM descriptors WHERE image_id = ?", (image_id,)).fetchone() is not None
 
     def read_cameras(self) -> Dict[int, dict]:
         """camera_id -> {model, width, height, params (float64), prior_focal_length} (database_sqlite.cc:2031-2038)."""

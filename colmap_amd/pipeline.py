@@ -173,6 +173,17 @@ def compare_reconstructions(reconstruction1, reconstruction2, alignment_error="r
     return None if result is None else {"rec2_from_rec1": result[1], "errors": result[0]}
 
 
+def extract_features(database_path, image_path, image_names=None, camera_model="SIMPLE_RADIAL", single_camera=False,
+                     camera_params="", sift_options=None, max_image_size=3200, default_focal_length_factor=1.2, gpu_index=0):
+    """pycolmap.extract_features (FeatureExtractorController, controllers/feature_extraction.cc) with the GPU SIFT
+    extractor (needs an MI355X): reads the images of image_path, writes cameras, images, keypoints and descriptors of
+    database_path (created if absent) and skips images that already have both. sift_options: a
+    feature_extraction.SiftExtractionOptions. Returns the counts of images extracted and skipped and of features."""
+    from . import feature_extractor as fe
+    return fe.extract_into_database(database_path, image_path, image_names, camera_model, single_camera, camera_params,
+                                    sift_options, max_image_size, default_focal_length_factor, gpu_index)
+
+
 def match_exhaustive(database_path, matching_options=None, block_size=50, gpu_index=0, cache_bytes=0, batch_pairs=None):
     """pycolmap.match_exhaustive (ExhaustiveFeatureMatcher, controllers/feature_matching.cc) without geometric
     verification: matches all image pairs of the database on the GPU (needs an MI355X) and writes the `matches` table;
