@@ -18,7 +18,7 @@ def _emul_lib():
     global _lib
     if _lib is None:
         so, src = os.path.join(EMUL, "libundistort_emul.so"), os.path.join(EMUL, "..", "..", "colmap_amd", "csrc")
-        deps = [os.path.join(src, f) for f in ("undistort.hip", "camera_projection.h")] + [os.path.join(EMUL, "hip", "hip_runtime.h"),
+        deps = [os.path.join(src, f) for f in ("undistort.hip", "undistort_plan.h", "camera_projection.h")] + [os.path.join(EMUL, "hip", "hip_runtime.h"),
                                                                                                  os.path.join(EMUL, "..", "..", "include", "colmap_amd", "camera_models.hpp")]
         if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
             subprocess.check_call(["sh", os.path.join(EMUL, "build_undistort.sh")])
@@ -76,3 +76,7 @@ def test_spherical_image():
 
 def test_batch_and_errors():
     G.case_batch_and_errors()
+
+
+def test_mixed_route_batch():
+    G.case_mixed_route_batch()

@@ -266,6 +266,38 @@ def case_batch_and_errors():
         U.UndistortImage(_options(), imgs[0], cams[0], gpu_index=4096)
 
 
+def case_mixed_route_batch():
+    """One call whose images take every route in turn -- indirect, direct, resize, clone, indirect again -- through one
+    set of grow-only device buffers: the last image reuses buffers that grew for the first, after smaller images. Every
+    output and output camera is byte-equal to the single-image call for the same input."""
+    lens = strong(ba_camera(R.OPENCV, 61, 47, (0.37, -0.21)), 4.0)
+    cams = [lens, ba_camera(R.PINHOLE, 24, 20), R.Camera(R.EQUIRECTANGULAR, 40, 20, [40.0, 20.0]),
+            R.Camera(R.EQUIRECTANGULAR, 16, 8, [16.0, 8.0]), lens]
+    imgs = [R.noise_image(61, 47, 3, 31), R.noise_image(24, 20, 1, 32), R.noise_image(40, 20, 3, 33),
+            R.noise_image(16, 8, 1, 34), R.noise_image(61, 47, 1, 35)]
+    routes = ["indirect", "direct", "resize", "clone", "indirect"]
+    opt = _options(max_image_size=20)
+    res = U.UndistortImages(opt, imgs, cams)
+    assert len(res) == 5
+    for k, ((got, oc), img, cam, route) in enumerate(zip(res, imgs, cams, routes)):
+        if cam.model_id == R.EQUIRECTANGULAR:
+            same_size = (oc.width, oc.height) == (cam.width, cam.height)
+            took = "clone" if same_size else "resize"
+            assert oc.model_id == R.EQUIRECTANGULAR and (not same_size or np.array_equal(got, img))
+        else:
+            took = "direct" if R.should_warp_directly(cam, oc) else "indirect"
+            assert oc.model_id == U.PINHOLE
+        assert took == route, (k, took, route)
+        alone, alone_cam = U.UndistortImage(opt, img, cam)
+        assert (oc.model_id, oc.width, oc.height) == (alone_cam.model_id, alone_cam.width, alone_cam.height), k
+        assert np.array_equal(oc.params, alone_cam.params), k
+        assert got.shape == alone.shape and got.dtype == alone.dtype and np.array_equal(got, alone), k
+        assert got.any(), k
+    assert (res[1][1].width, res[1][1].height) == (20, 17)
+    assert (res[2][1].width, res[2][1].height) == (20, 10)
+    assert max(res[0][1].width, res[0][1].height) == 20 and res[0][0].shape[2] == 3 and res[4][0].ndim == 2
+
+
 # ---- the GPU runs ----------------------------------------------------------------------------------------------------
 
 pytestmark = pytest.mark.gpu
@@ -307,6 +339,10 @@ def test_spherical_image():
 
 def test_batch_and_errors():
     case_batch_and_errors()
+
+
+def test_mixed_route_batch():
+    case_mixed_route_batch()
 
 
 def test_full_size_warp_parity():
